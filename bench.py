@@ -2,6 +2,7 @@
 """VideoPrism-Base bf16 forward throughput on MI355X (BASELINE.json metric/configs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload base|large|lvt_large|lvt_base] [--dtype bf16|f32]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,7 +14,14 @@ embeddings through the library's RCCL collective (vp_allgather).  value = clips 
 ranks / max-over-ranks time.  Without torch.distributed.run, `--gpus N > 1` spawns the N ranks
 itself (before any GPU call in the parent).
 
-Also reported (one JSON line on rank 0):
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the
+outputs if `--dump-outputs DIR` is given, and the result line (`roofline`, `cpu_baseline` null and
+`kernel_ms_per_step` empty).  `--dump-outputs DIR` writes what the last timed step returned to its
+caller as DIR/<name>.npy in float32 (rank 0; the token embeddings of the encoder workloads are a
+fixed, seeded sample of rows, at most 48 MB); the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
+
+With `--full` also reported (one JSON line on rank 0):
   roofline     the dominant kernel's algorithmic FLOP (or byte) rate, from HIP events recorded
                on its launch stream inside the timed region, against the MI355X dense peak; its
                HBM `traffic` from a PMC record of the same kernel symbol and the same sources
@@ -160,6 +168,27 @@ def load_traffic(path: str, symbol: str, workload: str, src_hash: str):
     return k.get("hbm_bytes_per_launch"), t.get("source")
 
 
+DUMP_MAX_ELEMS = 12 * 2 ** 20  # per array, float32: 48 MB
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    """--dump-outputs: every tensor of `outputs` as <path>/<name>.npy in float32.  An array above
+    DUMP_MAX_ELEMS is cut to a sample of its rows (all leading dimensions flattened), drawn without
+    replacement by a generator seeded with 0 and kept in ascending order: the same rows for the same
+    shape, whatever the build."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            t = t.reshape(-1, t.shape[-1])
+            keep = np.sort(np.random.default_rng(0).choice(t.shape[0], DUMP_MAX_ELEMS // t.shape[1],
+                                                           replace=False))
+            t = t[torch.from_numpy(keep).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -287,9 +316,15 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=None, help="clips per GPU")
     ap.add_argument("--queries", type=int, default=8, help="text queries (LvT workloads)")
     ap.add_argument("--frames", type=int, default=16)
-    ap.add_argument("--no-profile", action="store_true", help="no per-kernel HIP events")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-peak", action="store_true", help="skip the measured-MFMA-peak microbenchmark")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-kernel breakdown and the dominant kernel's roofline (HIP "
+                         "events), the measured MFMA peak and the CPU baseline; off by default")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the per-kernel HIP events")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-peak", action="store_true",
+                    help="--full without the measured-MFMA-peak microbenchmark")
     ap.add_argument("--no-allgather", action="store_true")
     ap.add_argument("--traffic", default=None,
                     help="PMC traffic record (default: the newest profiles/traffic_r*_<workload>.json "
@@ -409,7 +444,7 @@ def _run(args, rank: int, local_rank: int, world: int, owned: list) -> None:
     launches_per_fwd = 3 + 7 * (cfg["num_spatial_layers"] + cfg["num_temporal_layers"]) + 2
     if lvt:
         launches_per_fwd += 8 * cfg["num_auxiliary_layers"] + 4 + 8 * cfg["num_unimodal_layers"] + 8
-    profile = not (args.no_profile or args.standin)
+    profile = args.full and not (args.no_profile or args.standin)
     breakdown, dom_name, dom_symbol = {}, None, None
     if profile:
         # per-class breakdown from one extra profiled step outside the timed region (an event
@@ -434,8 +469,11 @@ def _run(args, rank: int, local_rank: int, world: int, owned: list) -> None:
     prof = eng.profile_read() if profile else {}
     if profile:
         eng.profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        outputs = dict(last) if lvt else dict(last, embeddings=out)
+        dump_outputs(args.dump_outputs, outputs)
 
-    clips = world * B * args.steps
+    clips =world * B * args.steps
     value = clips / elapsed
     ms_per_step = elapsed / args.steps * 1e3
     gpc = lvt_gflop_per_clip(cfg, T) if lvt else gflop_per_clip(cfg, T)
@@ -499,7 +537,7 @@ def _run(args, rank: int, local_rank: int, world: int, owned: list) -> None:
                                                      "median of 3 launches"})
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not lvt and not args.standin:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not lvt and not args.standin:
         cfg["_name"] = name
         cpu = cpu_baseline(cfg, variables)
 
@@ -542,7 +580,7 @@ def _run(args, rank: int, local_rank: int, world: int, owned: list) -> None:
             "cpu_baseline": cpu,
             "kernel_ms_per_step": kernel_ms,
             "kernel_ms_per_step_source": "HIP events around every launch of one extra step after "
-                                         "warmup (outside the timed region)",
+                                         "warmup (outside the timed region)" if profile else None,
         }
         if args.standin:
             line.update({"data": "CPU stand-in forward (--standin): plumbing test, not a measurement",

@@ -123,6 +123,12 @@ def g_full(tag, T=16, modes=("f64", "bf16")):
         # fp64 rows for the fp32 bar (1e-5); float32 storage would round them by up to ~1e-7 * |y|
         arrays[f"rows_{mode}"] = e[0, ::64].astype(np.float64 if T > 16 else np.float32)
         arrays[f"frame_mean_{mode}"] = e[0].reshape(T, -1, e.shape[-1]).mean(axis=1).astype(np.float32)
+    if T > 16:
+        # the fp64 rows of a long clip go into two files of their own (<tag>_rows0/1.npz: the first and
+        # the second half of the rows), which keeps every fixture file under 1 MiB
+        halves = {k: np.array_split(arrays.pop(k), 2) for k in [f"rows_{mode}" for mode in modes]}
+        for part in range(2):
+            np.savez_compressed(os.path.join(HERE, f"{tag}_rows{part}.npz"), **{k: h[part] for k, h in halves.items()})
     np.savez_compressed(os.path.join(HERE, f"{tag}.npz"), **arrays)
 
 

@@ -75,7 +75,7 @@ def _bench_env():
                                                              "MASTER_ADDR", "MASTER_PORT")}
 
 
-def _bench_standin(workload, batch, env_update=None):
+def _bench_standin(workload, batch, env_update=None, extra=()):
     import json
     import subprocess
     import sys
@@ -88,7 +88,7 @@ def _bench_standin(workload, batch, env_update=None):
             env[k] = v
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--standin",
                         "--workload", workload, "--batch", str(batch), "--frames", "2", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=150, env=env)
+                        "--warmup", "1", *extra], capture_output=True, text=True, timeout=150, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
     assert len(lines) == 1  # rank 0 only
@@ -121,14 +121,21 @@ def test_rank_env_keeps_an_explicit_ipc_mode():
 
 
 @pytest.mark.timeout(200)
-def test_bench_spawns_world2_lvt_similarity():
+def test_bench_spawns_world2_lvt_similarity(tmp_path):
     """LvT step: video embeddings -> gather -> similarity against the replicated text queries;
-    the similarity covers every clip of both ranks ([2*b, Q], README.md:81)."""
-    line = _bench_standin("lvt_base", 3)
+    the similarity covers every clip of both ranks ([2*b, Q], README.md:81).  --dump-outputs
+    leaves what the last step returned (rank 0): the gathered rows and the similarity, float32."""
+    import numpy as np
+    line = _bench_standin("lvt_base", 3, extra=("--dump-outputs", str(tmp_path / "out")))
     assert line["n_gpus"] == 2
     chk = line["standin_check"]
     assert chk["gathered_shape"] == [6, 768] and chk["row_order_ok"]
     assert chk["similarity_shape"] == [6, 8]
+    assert sorted(os.listdir(tmp_path / "out")) == ["rows.npy", "sim.npy"]
+    rows, sim = np.load(tmp_path / "out" / "rows.npy"), np.load(tmp_path / "out" / "sim.npy")
+    assert rows.dtype == np.float32 and rows.shape == (6, 768)
+    assert sim.dtype == np.float32 and sim.shape == (6, 8)
+    np.testing.assert_allclose(np.linalg.norm(rows, axis=1), 1.0, atol=1e-6)
 
 
 @pytest.mark.timeout(200)

@@ -1,4 +1,4 @@
-"""The driver's bench contract on the GPU: `python bench.py` (the configs[1] workload, a short run) prints
+"""The driver's bench contract on the GPU: `python bench.py --full` (the configs[1] workload, a short run) prints
 one JSON line with the fields the driver and the judge read -- metric / value / unit, the timing
 fields, `roofline` (achieved = algorithmic FLOPs per launch / live HIP-event launch time, frac =
 achieved / peak) and `traffic` quoted from the committed PMC record whenever that record was
@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_json_contract(cuda):
-    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                         "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -45,20 +45,28 @@ def test_bench_json_contract(cuda):
             assert rf["traffic"] is not None and rf["traffic"] > 0, rf
 
 
-def test_bench_under_torchrun_world1(cuda):
+def test_bench_under_torchrun_world1(cuda, tmp_path):
     """The driver's N > 1 launch form (torch.distributed.run, rendezvous on 127.0.0.1) at one rank: the
     launcher-provided RANK / WORLD_SIZE path of bench.py (gloo group for the barrier and the max over
-    ranks) prints the same contract line."""
+    ranks) prints the same contract line.  It is a plain run (no --full): the line carries the headline
+    fields only, and --dump-outputs leaves the last step's embeddings (a seeded sample of rows) in float32."""
     import socket
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-profile"],
+                        "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
                        cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["parallelism"].startswith("dp1")
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["dtype"] == "bf16" and d["unit"] == "clips/s"
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["kernel_ms_per_step"] == {}
+    import numpy as np
+    assert sorted(os.listdir(tmp_path / "out")) == ["embeddings.npy"]
+    emb = np.load(tmp_path / "out" / "embeddings.npy")
+    assert emb.dtype == np.float32 and emb.shape == (12 * 2 ** 20 // 768, 768) and emb.nbytes <= 64e6
+    assert np.isfinite(emb).all() and emb.std() > 0

@@ -43,7 +43,10 @@ def _pool_l2(e):
 
 def _setup(which):
     fname, model_name, cfg_key = LONG[which]
-    g = np.load(os.path.join(GOLD, fname), allow_pickle=False)
+    g = dict(np.load(os.path.join(GOLD, fname), allow_pickle=False))
+    # the fp64 rows are stored in two halves of their own (make_golden.py: every fixture file under 1 MiB)
+    g["rows_f64"] = np.concatenate([np.load(os.path.join(GOLD, fname.replace(".npz", f"_rows{part}.npz")),
+                                            allow_pickle=False)["rows_f64"] for part in range(2)])
     T = int(g["T"])
     var = params.synthetic_params(models.CONFIGS[cfg_key], seed=int(g["param_seed"]))
     video = np.random.default_rng(int(g["video_seed"])).random((1, T, 288, 288, 3), dtype=np.float32)

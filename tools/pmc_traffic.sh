@@ -20,7 +20,7 @@ i=0
 for P in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES"; do
   i=$((i+1))
   timeout -s KILL 240 rocprofv3 --pmc $P --output-format csv -d "$OUT/p$i" -o pmc -- \
-    python3 "$ROOT/bench.py" --workload "$WL" --dtype "$DT" --steps 2 --warmup 1 --no-cpu-baseline --no-peak > "$OUT/p$i.log" 2>&1
+    python3 "$ROOT/bench.py" --workload "$WL" --dtype "$DT" --steps 2 --warmup 1 --full --no-cpu-baseline --no-peak > "$OUT/p$i.log" 2>&1
 done
 python3 "$ROOT/tools/pmc_summary.py" "$OUT" --json "$REC" "$LABEL" > "$OUT/summary.txt"
 cat "$OUT/summary.txt"
