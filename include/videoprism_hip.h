@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define VP_ABI_VERSION 5
+#define VP_ABI_VERSION 6
 
 typedef struct vp_handle vp_handle;
 
@@ -171,6 +171,20 @@ int vp_op_layernorm(const void* x, int in_dtype, int64_t rows, int64_t D, const 
  * with features in (p, q, c) order and zero padding from P*P*C to kpad. */
 int vp_op_patchify(const void* video, int in_dtype, void* patches, int out_dtype, int64_t BT,
                    int64_t H, int64_t W, int64_t C, int64_t P, int64_t kpad, void* stream);
+
+enum vp_resize_mode { VP_RESIZE_CENTER_CROP = 0, VP_RESIZE_STRETCH = 1 };
+
+/* Replaces video_utils.py:76-87, 97-127 (cv2 BGR->RGB, cv2.resize INTER_LINEAR on uint8, center crop).
+ *   src        device uint8: frame n, row y, pixel x, channel c at n*frame_stride + y*row_stride + 3*x + c (bytes)
+ *   frame_idx  device int32 [F] (indices into the N source frames, clamped to [0, N-1]), or NULL = 0..F-1 (then F <= N)
+ *   dst        device uint8 [F, S, S, 3], contiguous
+ * VP_RESIZE_CENTER_CROP resizes the short side to S and keeps the centre S x S window (only the window
+ * is computed); VP_RESIZE_STRETCH resizes to S x S.  swap_rb != 0 swaps channels 0 and 2.  The arithmetic
+ * is cv2's 11-bit fixed point (tests/preprocess_restatement.py states it).  No handle: the call is
+ * asynchronous on `stream` on the current device, never allocates and never synchronises. */
+int vp_op_preprocess_frames(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
+                            int64_t frame_stride, const int32_t* frame_idx, int64_t F, int mode,
+                            int swap_rb, int64_t S, uint8_t* dst, void* stream);
 
 /* Build-defined pooled clip embedding used by the multi-GPU gather (the video-only encoder
  * has no pooler in the reference): out[b] = l2norm(mean_l emb[b, l, :]) in fp32, with the

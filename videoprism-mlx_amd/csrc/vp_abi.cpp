@@ -713,6 +713,29 @@ int vp_op_patchify(const void* video, int in_dtype, void* patches, int out_dtype
   return VP_OK;
 }
 
+int vp_op_preprocess_frames(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
+                            int64_t frame_stride, const int32_t* frame_idx, int64_t F, int mode,
+                            int swap_rb, int64_t S, uint8_t* dst, void* stream) {
+  using namespace vp;
+  if (!src || !dst) return fail(VP_EINVAL, "null argument");
+  if (N < 1 || H < 1 || W < 1 || F < 1 || S < 1) return fail(VP_EINVAL, "N, H, W, F and S must be at least 1");
+  if (mode != VP_RESIZE_CENTER_CROP && mode != VP_RESIZE_STRETCH)
+    return fail(VP_EINVAL, "Unknown resize_mode: " + std::to_string(mode));
+  if (H >= (1 << 24) || W >= (1 << 24) || S > 16384 || N > INT32_MAX || F > INT32_MAX)
+    return fail(VP_EINVAL, "frame geometry out of range (H, W < 2^24, S <= 16384, N, F < 2^31)");
+  if (row_stride < 3 * W) return fail(VP_EINVAL, "row_stride must be at least 3*W bytes");
+  if (frame_stride < H * row_stride) return fail(VP_EINVAL, "frame_stride must be at least H*row_stride bytes");
+  if (!frame_idx && F > N)
+    return fail(VP_EINVAL, "Video has only " + std::to_string(N) + " frames, but " + std::to_string(F) + " requested");
+  int64_t nh, nw, y0, x0;
+  if (const char* why = preprocess_geometry(H, W, S, mode, &nh, &nw, &y0, &x0)) return fail(VP_EINVAL, why);
+  hipError_t e = preprocess_frames(src, N, H, W, row_stride, frame_stride, frame_idx, F, mode, swap_rb, S, dst,
+                                   static_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) return fail(VP_EINVAL, "too many output pixels for one launch");
+  VP_HIP(e);
+  return VP_OK;
+}
+
 int vp_op_pool_l2(const void* emb, int dtype, int64_t B, int64_t L, int64_t D, float* out,
                   void* stream) {
   using namespace vp;

@@ -211,4 +211,15 @@ hipError_t similarity(const float* a, const float* b, int B, int Q, int D, float
 
 hipError_t pool_l2(const void* emb, int is_bf16, int B, int L, int D, float* out, hipStream_t s);
 
+// ---- frame ingest (preprocess.hip) ----
+// video_utils.py:109-124: size of the resized frame and the crop window's origin in it (mode 0 centre
+// crop, 1 stretch to S x S); a message if this library's kernel cannot take the geometry, else nullptr
+const char* preprocess_geometry(int64_t H, int64_t W, int64_t S, int mode, int64_t* new_h, int64_t* new_w,
+                                int64_t* y0, int64_t* x0);
+// uint8 frames (frame n, row y, pixel x, channel c at n*frame_stride + y*row_stride + 3x + c) gathered by
+// frame_idx (nullable: 0..F-1), resized as cv2.resize does on uint8 and cropped -> dst uint8 [F, S, S, 3]
+hipError_t preprocess_frames(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
+                             int64_t frame_stride, const int32_t* frame_idx, int64_t F, int mode, int swap_rb,
+                             int64_t S, uint8_t* dst, hipStream_t s);
+
 }  // namespace vp

@@ -24,6 +24,7 @@ EPI_STORE, EPI_GELU, EPI_RESID, EPI_POS, EPI_RESID_FFN = 0, 1, 2, 3, 4
 # bf16 residual stream variants (bf16 resid / out; bf16 precision only)
 EPI_RESID_BF16, EPI_POS_BF16, EPI_RESID_FFN_BF16 = 5, 6, 7
 PERM_NONE, PERM_BTN_TO_BNT, PERM_BNT_TO_BTN = 0, 1, 2
+VP_RESIZE_CENTER_CROP, VP_RESIZE_STRETCH = 0, 1
 
 
 class NativeLibraryError(RuntimeError):
@@ -99,6 +100,8 @@ _SIGNATURES = {
                                 c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     "vp_op_patchify": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64,
                                c_int64, c_int64, c_void_p]),
+    "vp_op_preprocess_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                        c_int64, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "vp_op_pool_l2": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "vp_op_attention_masked": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float,
                                        c_void_p, c_int, c_void_p]),
@@ -410,6 +413,34 @@ def op_patchify(video, P, kpad, out_dtype=None, stream=None):
     out = torch.empty((BT * (H // P) * (W // P), kpad), dtype=out_dtype, device=video.device)
     call("vp_op_patchify", _ptr(video), _prec(video), _ptr(out),
          VP_BF16 if out_dtype == torch.bfloat16 else VP_F32, BT, H, W, C, P, kpad, _stream(stream))
+    return out
+
+
+def op_preprocess_frames(src, frame_idx=None, mode=VP_RESIZE_CENTER_CROP, swap_rb=False, size=288, out=None,
+                         stream=None):
+    """uint8 frames [N, H, W, 3] (any frame and row strides: views work) -> uint8 [F, size, size, 3],
+    resized as cv2.resize does on uint8 and centre-cropped (or stretched); frame_idx int32 [F] on the
+    device picks the frames (None: all N in order)."""
+    import torch
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f"frames must be uint8 [N, H, W, 3], got {src.dtype} {tuple(src.shape)}")
+    N, H, W, _ = src.shape
+    if src.stride(3) != 1 or (W > 1 and src.stride(2) != 3):
+        raise ValueError("frames must have packed pixels (channel stride 1, pixel stride 3)")
+    # a dimension of extent 1 may carry any stride: give the packed one
+    row_stride = src.stride(1) if H > 1 else 3 * W
+    frame_stride = src.stride(0) if N > 1 else H * row_stride
+    if frame_idx is not None and (frame_idx.dtype != torch.int32 or frame_idx.dim() != 1 or
+                                  not frame_idx.is_contiguous() or frame_idx.device != src.device):
+        raise ValueError("frame_idx must be a contiguous int32 vector on the frames' device")
+    F = N if frame_idx is None else frame_idx.shape[0]
+    if out is None:
+        out = torch.empty((F, size, size, 3), dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F, size, size, 3) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous uint8 {(F, size, size, 3)}")
+    with torch.cuda.device(src.device):  # the entry point has no handle: it launches on the current device
+        call("vp_op_preprocess_frames", _ptr(src), N, H, W, row_stride, frame_stride, _ptr(frame_idx), F, int(mode),
+             1 if swap_rb else 0, size, _ptr(out), _stream(stream))
     return out
 
 
