@@ -152,12 +152,15 @@ int vp_op_gemm(int precision, int epilogue, const void* A, int64_t lda, const vo
 
 /* Capped attention over rows qkv[num_seq*S, 3*heads*64] = [q|k|v] (q pre-scaled), writing
  * o[num_seq*S, heads*64].  Replaces DotProductAttention._dot_atten (layers.py:601-661).
- * precision VP_BF16 (S <= 256: the spatial kernel at S == 256, the temporal kernel at S <= 16,
- * the sequence-packed kernel between; any S > 256 without key_pad: the long-sequence kernel of the LvT
- * auxiliary encoder; S > 256 with key_pad: the online-softmax kernel of vp_op_attention_masked, as the
- * forward runs it) or VP_F32 (S <= 256).  key_pad: [num_seq*S] or NULL.
- * bf16 with a cap outside (0, 50] (no capping, or one whose unnormalised fp32 numerators could
- * overflow) runs the online-softmax kernel of vp_op_attention_masked, any S. */
+ * key_pad: [num_seq*S] (1 = padded key) or NULL.  Any S >= 1 in both precisions; the kernel is the one the
+ * forward runs for such a stack (one dispatch serves both), first match:
+ *   VP_BF16  cap outside (0, 50] (no capping, or a cap whose unnormalised fp32 numerators could overflow):
+ *              the online-softmax kernel of vp_op_attention_masked
+ *            S > 256 without key_pad: the long-sequence kernel of the LvT auxiliary encoder
+ *            S == 256: the spatial kernel; S <= 16: the temporal kernel; 16 < S < 256: the sequence-packed
+ *              kernel; S > 256 with key_pad: the online-softmax kernel
+ *   VP_F32   S <= 256: the fp32 kernel (on the MFMA for S >= 128 with 0 < cap <= 50)
+ *            S > 256: the fp32 MFMA kernel for 0 < cap <= 50, else the online-softmax kernel */
 int vp_op_attention(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S,
                     int64_t heads, float cap, const float* key_pad, void* stream);
 

@@ -7,7 +7,8 @@ The model, weights and inputs are built from seeds inside the run, so both trees
 inputs.  Covered: Base full depth T = 16 bf16 (the bench's path), Base 2+1 layers at T = 8 / 20 /
 32 in bf16 and fp32 (precomputed temporal tables and the generic temporal attention), Large 1+1
 layers at T = 16 bf16 (8 -> 16 temporal interpolation), LvT-Base reduced depth at 288 x 288, T = 4 / 16
-(auxiliary attention over 1024 / 4096 tokens) in bf16 and fp32: video, frame and text embeddings.
+(auxiliary attention over 1024 / 4096 tokens) in bf16 and fp32: video, frame and text embeddings; the
+classifier on Base 1+1 layers in bf16 and fp32: logits, global embeddings and feature maps.
 """
 import hashlib
 import json
@@ -71,4 +72,24 @@ def run_lvt(T, bf16, B=2, seed=3):
 for T in (4, 16):
     for bf16 in (False, True):
         out[f"lvt_base_t{T}_{'bf16' if bf16 else 'f32'}"] = run_lvt(T, bf16)
+
+
+def run_classifier(bf16, seed=4):
+    """Classifier on Base 1+1 layers, 40 classes, T = 2: logits, global embeddings and both feature maps."""
+    enc = dict(base, num_spatial_layers=1, num_temporal_layers=1)
+    m = models.get_model(None, model_fn=lambda: encoders.FactorizedVideoClassifier(encoder_params=enc, num_classes=40),
+                         fprop_dtype=torch.bfloat16 if bf16 else None)
+    var = params.synthetic_params(enc, seed, specs=m.param_specs())
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    video = torch.rand((2, 2, 288, 288, 3), generator=g, device="cuda")
+    logits, outs = m.apply(var, video.to(torch.bfloat16) if bf16 else video, return_intermediate=True)
+    torch.cuda.synchronize()
+    h = hashlib.sha256()
+    for a in (logits, *(outs[k] for k in sorted(outs))):
+        h.update(a.contiguous().view(torch.uint8).cpu().numpy().tobytes())
+    return h.hexdigest()[:16]
+
+
+for bf16 in (False, True):
+    out[f"classifier_base11_t2_{'bf16' if bf16 else 'f32'}"] = run_classifier(bf16)
 print(json.dumps(out))

@@ -52,9 +52,7 @@ int vp_dev_gemm_tattn_abl(int which, int abl, const void* A, const void* W, int6
   using namespace vp;
   EpiArgs ep;
   ep.out = out; ep.ldo = K; ep.bias = bias; ep.ln_rs = ln_rs; ep.ln_c = ln_c; ep.resid = p;
-  ep.cap = cap; ep.heads = (int)heads;
-  ep.cap_c1 = 2.0f * 1.4426950408889634f / cap;
-  ep.cap_c2 = cap * 1.4426950408889634f;
+  vpi::set_tattn_cap(ep, cap, (int)heads);
   VP_HIP(gemm_bf16_w4_tattn_abl(which, abl, (const bf16_t*)A, (const bf16_t*)W, (int)M, (int)(which == 0 ? 2 * K : K),
                                 (int)K, ep, static_cast<hipStream_t>(stream)));
   return VP_OK;

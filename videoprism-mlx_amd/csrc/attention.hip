@@ -16,8 +16,21 @@
 //   ds_read_b64_tr_b16), so P never touches LDS and the row sum is lane-local.
 // attention_temporal_bf16: S = T <= 16 frames.  One wave per (sequence, head), 16x16x32 for
 //   Q.K^T and 16x16x16 for P.V; memory-bound on the qkv rows.
-// attention_f32: fp32 path (fprop_dtype=float32): S = 256 with 0 < cap <= 50 on v_mfma_f32_32x32x2f32
-//   (attn_f32_mfma_kernel), any other S <= 256 / cap on a generic online-softmax kernel; exact tanhf/expf.
+// attention_seq_bf16: 16 < S <= 256 (clips longer than 16 frames, other patch grids, the text tower with
+//   its causal mask): sequences packed into the spatial kernel's 256-key tile.
+// attention_f32: fp32 path (fprop_dtype=float32), any S <= 256: S >= 128 with 0 < cap <= 50 on
+//   v_mfma_f32_32x32x2f32 (attention_f32_mfma), anything else on a generic online-softmax kernel with exact
+//   tanhf/expf.
+// attention_f32_mfma: fp32, any S >= 1 with 0 < cap <= 50 (max-free softmax; numerators from
+//   capped_exp_f32x16, a tanh fit and a compensated exp2 within a few fp32 ulp); used from S >= 128, by the auxiliary encoder at any S.
+// Which of these (and attention_long.hip's attention_long_bf16 / attention_masked) a stack runs is decided in
+// one place, vp_internal.h choose_attention; first match:
+//   text tower       bf16, 0 < cap <= 50, 16 < S <= 256: seq (causal); otherwise masked (causal)
+//   bf16, other caps masked (cap <= 0 or cap > 50: no max-free softmax)
+//   auxiliary, fp32  0 < cap <= 50: f32_mfma; otherwise masked
+//   auxiliary, bf16  S >= 256: long; S > 16: seq; otherwise temporal
+//   video, fp32      S <= 256: f32; longer: f32_mfma for 0 < cap <= 50, otherwise masked
+//   video, bf16      S == 256: spatial; S <= 16: temporal; S < 256: seq; longer: masked
 #include <type_traits>
 
 #include "vp_common.h"

@@ -44,14 +44,27 @@ std::vector<float> temporal_table(const vp_handle* h, int T) {
   return dst;
 }
 
+// the encoder's leaves under h->prefix (encoders.py:391-580)
+void build_expected(vp_handle* h) {
+  const vp_config& c = h->cfg;
+  const int64_t D = c.model_dim, F = c.mlp_dim, NH = c.num_heads;
+  const int64_t P = c.patch_size;
+  const std::string& px = h->prefix;
+  h->expect(px + "patch_projection/linear/kernel", {P * P * 3, D});
+  h->expect(px + "patch_projection/linear/bias", {D});
+  h->expect(px + "spatial_pos_emb/emb_var", {(int64_t)c.pos_emb_h * c.pos_emb_w, D});
+  add_stack_expected(*h, px + "spatial_encoder/transformers_stack/x_layers/", c.num_spatial_layers, D, F, NH);
+  h->expect(px + "spatial_ln/scale", {D});
+  h->expect(px + "spatial_ln/bias", {D});
+  h->expect(px + "temporal_pos_emb/emb_var", {(int64_t)c.pos_emb_t, D});
+  add_stack_expected(*h, px + "temporal_encoder/transformers_stack/x_layers/", c.num_temporal_layers, D, F, NH);
+  h->expect(px + "temporal_ln/scale", {D});
+  h->expect(px + "temporal_ln/bias", {D});
+}
+
 }  // namespace
 
-extern "C" {
-
-const char* vp_last_error(void) { return g_err.c_str(); }
-int vp_abi_version(void) { return VP_ABI_VERSION; }
-
-int vp_create(const vp_config* cfg, int device, vp_handle** out) {
+int vpi::create_encoder(const vp_config* cfg, int device, const std::string& prefix, vp_handle** out) {
   if (!cfg || !out) return fail(VP_EINVAL, "null argument");
   *out = nullptr;
   if (cfg->num_heads <= 0 || cfg->model_dim % cfg->num_heads)
@@ -72,15 +85,22 @@ int vp_create(const vp_config* cfg, int device, vp_handle** out) {
   vp_handle* h = new vp_handle();
   h->cfg = *cfg;
   h->device = device;
+  h->prefix = prefix;
   build_expected(h);
   *out = h;
   return VP_OK;
 }
 
+extern "C" {
+
+const char* vp_last_error(void) { return g_err.c_str(); }
+int vp_abi_version(void) { return VP_ABI_VERSION; }
+
+int vp_create(const vp_config* cfg, int device, vp_handle** out) { return create_encoder(cfg, device, "", out); }
+
 int vp_destroy(vp_handle* h) {
   if (!h) return VP_OK;
-  hipSetDevice(h->device);
-  for (auto& a : h->allocs) hipFree(a.p);
+  h->free_all();
   for (auto& e : h->prof.ev) hipEventDestroy(e);
   delete h;
   return VP_OK;
@@ -98,50 +118,29 @@ int vp_param_name(const vp_handle* h, int index, const char** name) {
   return VP_OK;
 }
 
-int vp_set_param(vp_handle* h, const char* name, const float* host_data, const int64_t* shape,
-                 int ndim) {
-  if (!h || !name || !host_data || (ndim > 0 && !shape)) return fail(VP_EINVAL, "null argument");
-  if (h->finalized) return fail(VP_ESTATE, "handle already finalized");
-  auto it = h->expected.find(name);
-  if (it == h->expected.end()) return fail(VP_EINVAL, std::string("unexpected parameter: ") + name);
-  const auto& exp = it->second;
-  bool ok = (int)exp.size() == ndim;
-  for (int i = 0; ok && i < ndim; ++i) ok = exp[i] == shape[i];
-  if (!ok) {
-    std::string e = std::string("shape mismatch for ") + name + ": expected (";
-    for (size_t i = 0; i < exp.size(); ++i) e += std::to_string(exp[i]) + (i + 1 < exp.size() ? ", " : "");
-    e += ") got (";
-    for (int i = 0; i < ndim; ++i) e += std::to_string(shape[i]) + (i + 1 < ndim ? ", " : "");
-    return fail(VP_EINVAL, e + ")");
-  }
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  HostParam hp;
-  hp.shape.assign(shape, shape + ndim);
-  hp.data.assign(host_data, host_data + n);
-  h->host[name] = std::move(hp);
-  return VP_OK;
+int vp_set_param(vp_handle* h, const char* name, const float* host_data, const int64_t* shape, int ndim) {
+  return h ? h->set(name, host_data, shape, ndim) : fail(VP_EINVAL, "null argument");
 }
 
 int vp_finalize(vp_handle* h) {
   if (!h) return fail(VP_EINVAL, "null handle");
   if (h->finalized) return VP_OK;
-  for (const auto& n : h->names)
-    if (!h->host.count(n)) return fail(VP_ESTATE, "missing parameter: " + n);
+  if (const std::string* n = h->first_missing()) return fail(VP_ESTATE, "missing parameter: " + *n);
   VP_HIP(hipSetDevice(h->device));
   const vp_config& c = h->cfg;
+  const bool bf = h->bf16();
   const int64_t D = c.model_dim, P = c.patch_size;
   const int64_t kreal = P * P * 3;
   h->kpad = (int)(((kreal + 63) / 64) * 64);
   int rc;
   const std::string& px = h->prefix;
   {  // patch projection: kernel [kreal][D] -> [D][kpad]
-    const auto& k = param_data(h, px + "patch_projection/linear/kernel");
+    const auto& k = h->data(px + "patch_projection/linear/kernel");
     std::vector<float> t((size_t)D * h->kpad, 0.0f);
     for (int64_t i = 0; i < kreal; ++i)
       for (int64_t n = 0; n < D; ++n) t[(size_t)n * h->kpad + i] = k[(size_t)i * D + n];
-    if ((rc = upload_mat(h, t, &h->wpatch))) return rc;
-    if (is_bf16(h) && vp::video_patch_ok((int)P)) {  // the frames' chunk order (gemm_bf16_w4_video, vp_kernels.h)
+    if ((rc = h->upload_mat(t, bf, &h->wpatch))) return rc;
+    if (bf && vp::video_patch_ok((int)P)) {  // the frames' chunk order (gemm_bf16_w4_video, vp_kernels.h)
       const int64_t cpr = vp::video_patch_cpr((int)P), kv = vp::video_patch_k((int)P);
       std::vector<float> tv((size_t)D * kv, 0.0f);
       for (int64_t py = 0; py < P; ++py)
@@ -153,14 +152,14 @@ int vp_finalize(vp_handle* h) {
             for (int64_t n = 0; n < D; ++n) tv[(size_t)n * kv + 64 * py + 8 * cr + e] = k[(size_t)(py * 3 * P + v) * D + n];
           }
         }
-      if ((rc = upload_mat(h, tv, &h->wpatch_v))) return rc;
+      if ((rc = h->upload_mat(tv, bf, &h->wpatch_v))) return rc;
     }
-    if ((rc = upload_f32(h, param_data(h, px + "patch_projection/linear/bias"), &h->bpatch))) return rc;
+    if ((rc = h->upload_f32(h->data(px + "patch_projection/linear/bias"), &h->bpatch))) return rc;
   }
-  if ((rc = upload_f32(h, param_data(h, px + "spatial_pos_emb/emb_var"), &h->spatial_pos))) return rc;
-  h->spatial_pos_host = param_data(h, px + "spatial_pos_emb/emb_var");
+  if ((rc = h->upload_f32(h->data(px + "spatial_pos_emb/emb_var"), &h->spatial_pos))) return rc;
+  h->spatial_pos_host = h->data(px + "spatial_pos_emb/emb_var");
   {  // temporal positional tables for T = 1..kPrecomputedT in one buffer (encoders.py:543-553)
-    h->temporal_pos_host = param_data(h, px + "temporal_pos_emb/emb_var");
+    h->temporal_pos_host = h->data(px + "temporal_pos_emb/emb_var");
     std::vector<float> tab;
     std::vector<size_t> off(kPrecomputedT + 1);
     for (int T = 1; T <= kPrecomputedT; ++T) {
@@ -169,29 +168,28 @@ int vp_finalize(vp_handle* h) {
       tab.insert(tab.end(), t.begin(), t.end());
     }
     float* dev = nullptr;
-    if ((rc = upload_f32(h, tab, &dev))) return rc;
+    if ((rc = h->upload_f32(tab, &dev))) return rc;
     for (int T = 1; T <= kPrecomputedT; ++T) h->temporal_pos[T] = dev + off[T];
   }
-  const bool fold = is_bf16(h);
-  if ((rc = pack_stack(h, px + "spatial_encoder/transformers_stack/x_layers/", c.num_spatial_layers, D, c.mlp_dim,
+  const bool fold = bf;  // LayerNorms folded into the consuming GEMMs
+  if ((rc = pack_stack(*h, bf, px + "spatial_encoder/transformers_stack/x_layers/", c.num_spatial_layers, D, c.mlp_dim,
                        c.num_heads, fold, h->spatial, QKV_BLOCKED)))
     return rc;
-  if ((rc = pack_stack(h, px + "temporal_encoder/transformers_stack/x_layers/", c.num_temporal_layers, D,
+  if ((rc = pack_stack(*h, bf, px + "temporal_encoder/transformers_stack/x_layers/", c.num_temporal_layers, D,
                        c.mlp_dim, c.num_heads, fold, h->temporal,
                        fold && c.model_dim == c.num_heads * 64 ? QKV_PER_HEAD : QKV_PLAIN)))
     return rc;
   std::vector<float> g(D);
   const char* lns[2] = {"spatial_ln", "temporal_ln"};
   for (int i = 0; i < 2; ++i) {
-    const auto& sc = param_data(h, px + lns[i] + "/scale");
+    const auto& sc = h->data(px + lns[i] + "/scale");
     for (int64_t d = 0; d < D; ++d) g[d] = sc[d] + 1.0f;
     float** gp = i == 0 ? &h->sln_g : &h->tln_g;
     float** bp = i == 0 ? &h->sln_b : &h->tln_b;
-    if ((rc = upload_f32(h, g, gp)) || (rc = upload_f32(h, param_data(h, px + lns[i] + "/bias"), bp)))
+    if ((rc = h->upload_f32(g, gp)) || (rc = h->upload_f32(h->data(px + lns[i] + "/bias"), bp)))
       return rc;
   }
-  h->host.clear();
-  h->finalized = true;
+  h->seal();
   return VP_OK;
 }
 
@@ -200,9 +198,7 @@ int vp_prepare_geometry(vp_handle* h, int64_t H, int64_t W) {
   if (!h->finalized) return fail(VP_ESTATE, "vp_finalize has not been called");
   const vp_config& c = h->cfg;
   const int64_t P = c.patch_size, D = c.model_dim;
-  if (H < 1 || W < 1 || H % P || W % P)
-    return fail(VP_EINVAL, "Image height (" + std::to_string(H) + ") and width (" + std::to_string(W) +
-                               ") should be multiples of patch_size (" + std::to_string(P) + ").");
+  if (H < 1 || W < 1 || H % P || W % P) return fail(VP_EINVAL, patch_size_message(H, W, P));
   const int gm = (int)(H / P), gn = (int)(W / P);
   if ((gm == c.pos_emb_h && gn == c.pos_emb_w) || h->grid_pos.count({gm, gn})) return VP_OK;
   // _interpolate_emb_2d (encoders.py:133-165): separable jax.image.resize 'bilinear' (antialiased
@@ -229,7 +225,7 @@ int vp_prepare_geometry(vp_handle* h, int64_t H, int64_t W) {
     }
   VP_HIP(hipSetDevice(h->device));
   float* dev = nullptr;
-  int rc = upload_f32(h, out, &dev);
+  int rc = h->upload_f32(out, &dev);
   if (rc) return rc;
   h->grid_pos[{gm, gn}] = dev;
   return VP_OK;
@@ -242,7 +238,7 @@ int vp_prepare_frames(vp_handle* h, int64_t T) {
   if (h->temporal_pos.count((int)T)) return VP_OK;
   VP_HIP(hipSetDevice(h->device));
   float* dev = nullptr;
-  int rc = upload_f32(h, temporal_table(h, (int)T), &dev);
+  int rc = h->upload_f32(temporal_table(h, (int)T), &dev);
   if (rc) return rc;
   h->temporal_pos[(int)T] = dev;
   return VP_OK;
@@ -321,13 +317,11 @@ int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int6
   const char* ge = bf ? gemm_bf16_check(Mp, 3 * D, D, D, D) : gemm_f32_check(Mp, 3 * D, D, D, D);
   if (ge) return fail(VP_ENOTSUP, ge);
   const double dM = M, dD = D, dE = (double)es;
-  auto gbytes = [&](double K, double N, double outb, double resid) {  // algorithmic GEMM bytes
-    return dM * K * dE + N * K * dE + dM * N * outb + dM * N * resid;
-  };
+  auto gbytes = [&](double K, double N, double outb, double resid) { return gemm_bytes(dM, K, N, dE, outb, resid); };
 
   // 1. tokenisation + patch projection + spatial pos-emb (encoders.py:436-514)
   const double kreal = (double)P_ * P_ * 3;
-  const double in_es = in_dtype == VP_U8 ? 1 : in_dtype == VP_BF16 ? 2 : 4;
+  const double in_es = (double)dtype_bytes(in_dtype);
   const bool fold = bf && c.num_spatial_layers > 0;  // LN1 of spatial layer 0 folded
   // bf16 on a 16x16 patch grid: the patch embedding reads the frames themselves (no patch
   // tensor); f32 / uint8 frames are converted to bf16 frames first (the patchify kernels' per-value
@@ -342,8 +336,7 @@ int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int6
         return video_to_bf16(video, in_dtype, static_cast<bf16_t*>(big), (int64_t)B * T * H * W * 3, s); }));
       frames = static_cast<const bf16_t*>(big);
     }
-    EpiArgs ep;
-    ep.out = x; ep.ldo = D; ep.bias = h->bpatch; ep.pos = sp_pos; ep.pos_rows = Nsp;
+    EpiArgs ep = epi_args(x, D, h->bpatch, nullptr, 0, sp_pos, Nsp, nullptr);
     ep.st_part = f.st_part; ep.st_rows = Mp;
     VP_HIP(f.rec(PC_GEMM_PATCH, 2.0 * dM * kreal * dD, gbytes(kreal, dD, dE, 0), [&] {
       return gemm_bf16_w4_video(fold ? EPI_POS_BF16_ST : EPI_POS_BF16, frames, P_, (const bf16_t*)h->wpatch_v, Mp, D,
@@ -368,7 +361,7 @@ int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int6
   if ((rc = run_stack(h->spatial, x, (int)(B * T), Nsp, pad_btn))) return rc;
   // 3. spatial_ln (+ optional spatial_features), transpose to (b n) t, + temporal pos-emb
   if (spatial_out)
-    VP_HIP(rec(PC_LAYERNORM, 0.0, dM * dD * dE + dM * dD * (out_dtype == VP_BF16 ? 2 : 4), [&] {
+    VP_HIP(rec(PC_LAYERNORM, 0.0, dM * dD * dE + dM * dD * (double)dtype_bytes(out_dtype), [&] {
       return layernorm(x, bf, M, D, h->sln_g, h->sln_b, spatial_out, out_dtype == VP_BF16, PERM_NONE, 1, 1, nullptr, s); }));
   VP_HIP(rec(PC_LAYERNORM, 0.0, ln_bytes, [&] {
     return layernorm(x, bf, M, D, h->sln_g, h->sln_b, x2, bf, PERM_BTN_TO_BNT, (int)T, Nsp, tpos, s,
@@ -376,7 +369,7 @@ int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int6
   // 4. temporal encoder over (b n) sequences of T tokens
   if ((rc = run_stack(h->temporal, x2, (int)(B * Nsp), (int)T, pad_bnt))) return rc;
   // 5. temporal_ln and '(bn)td->b(tn)d'
-  VP_HIP(rec(PC_LAYERNORM, 0.0, dM * dD * dE + dM * dD * (out_dtype == VP_BF16 ? 2 : 4), [&] {
+  VP_HIP(rec(PC_LAYERNORM, 0.0, dM * dD * dE + dM * dD * (double)dtype_bytes(out_dtype), [&] {
     return layernorm(x2, bf, M, D, h->tln_g, h->tln_b, out, out_dtype == VP_BF16, PERM_BNT_TO_BTN, (int)T, Nsp, nullptr, s); }));
   (void)es;
   return VP_OK;
@@ -391,27 +384,16 @@ int vp_forward(vp_handle* h, const void* video, int in_dtype, int64_t B, int64_t
                void* spatial_out, void* workspace, size_t ws_bytes, void* stream) {
   if (!h || !video || !out || !workspace) return fail(VP_EINVAL, "null argument");
   if (!h->finalized) return fail(VP_ESTATE, "vp_finalize has not been called");
-  if ((in_dtype != VP_F32 && in_dtype != VP_BF16 && in_dtype != VP_U8) ||
-      (out_dtype != VP_F32 && out_dtype != VP_BF16))
-    return fail(VP_EINVAL, "bad dtype");
-  int rc = check_geometry(h, B, T, H, W);
-  if (rc) return rc;
-  const int64_t Bc = chunk_of(h, B, T, H, W);
-  const size_t need = ws_layout(h, Bc, T, H, W).total;
-  if (ws_bytes < need) return fail(VP_EINVAL, "workspace too small: need " + std::to_string(need));
-  // per-clip strides of the caller's buffers
-  const int64_t P = h->cfg.patch_size, D = h->cfg.model_dim;
-  const size_t in_clip = (size_t)(T * H * W * 3) * (in_dtype == VP_U8 ? 1 : in_dtype == VP_BF16 ? 2 : 4);
-  const size_t out_clip = (size_t)(T * (H / P) * (W / P) * D) * (out_dtype == VP_BF16 ? 2 : 4);
-  for (int64_t b0 = 0; b0 < B; b0 += Bc) {
-    const int64_t nb = std::min(Bc, B - b0);
-    rc = forward_chunk(h, static_cast<const char*>(video) + b0 * in_clip, in_dtype, nb, T, H, W,
-                       frame_paddings ? frame_paddings + b0 * T : nullptr, static_cast<char*>(out) + b0 * out_clip,
-                       out_dtype, spatial_out ? static_cast<char*>(spatial_out) + b0 * out_clip : nullptr,
-                       workspace, stream);
-    if (rc) return rc;
-  }
-  return VP_OK;
+  size_t need = 0, out_clip = 0;
+  int rc = check_dtypes(in_dtype, out_dtype, false, h->cfg.fprop_dtype);
+  if (rc || (rc = vp_workspace_bytes(h, B, T, H, W, &need)) ||
+      (rc = check_workspace(h, T, H, W, ws_bytes, need, out_dtype, &out_clip)))
+    return rc;
+  const size_t in_clip = video_clip_bytes(T, H, W, in_dtype);
+  return for_each_chunk(h, B, T, H, W, [&](int64_t b0, int64_t nb) {
+    return forward_chunk(h, advance(video, b0 * in_clip), in_dtype, nb, T, H, W, advance(frame_paddings, b0 * T * 4),
+                         advance(out, b0 * out_clip), out_dtype, advance(spatial_out, b0 * out_clip), workspace, stream);
+  });
 }
 
 // ----------------------------------- profiling ----------------------------------------
@@ -498,9 +480,7 @@ int vp_op_gemm(int precision, int epilogue, const void* A, int64_t lda, const vo
   if ((epilogue == EPI_POS_F32 || epilogue == EPI_POS_BF16) && (!pos || pos_rows < 1))
     return fail(VP_EINVAL, "pos required");
   if (precision == VP_F32 && epilogue > 4) return fail(VP_EINVAL, "bf16 residual epilogues need precision VP_BF16");
-  EpiArgs ep;
-  ep.out = out; ep.ldo = ldo; ep.bias = bias; ep.resid = resid; ep.ldr = ldr;
-  ep.pos = pos; ep.pos_rows = (int)pos_rows; ep.rowpad = rowpad;
+  const EpiArgs ep = epi_args(out, ldo, bias, resid, ldr, pos, pos_rows, rowpad);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (precision == VP_BF16) {
     const char* e = gemm_bf16_check((int)M, (int)N, (int)K, lda, ldw);
@@ -525,9 +505,7 @@ int vp_dev_gemm_kernel(int which, int epi, const void* A, const void* W, int64_t
   const char* e = which == 1 ? nullptr : (which == 32 || which == 33) ? gemm_f32_check((int)M, (int)N, (int)K, K, K)
                                                                        : gemm_bf16_check((int)M, (int)N, (int)K, K, K);
   if (e) return fail(VP_EINVAL, e);
-  EpiArgs ep;
-  ep.out = out; ep.ldo = N; ep.bias = bias; ep.resid = resid; ep.ldr = N;
-  ep.pos = pos; ep.pos_rows = (int)(pos_rows > 0 ? pos_rows : 1); ep.rowpad = rowpad;
+  const EpiArgs ep = epi_args(out, N, bias, resid, N, pos, pos_rows > 0 ? pos_rows : 1, rowpad);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (which == 4)
     VP_HIP(gemm_bf16_w4(epi, (const bf16_t*)A, K, (const bf16_t*)W, K, (int)M, (int)N, (int)K, ep, s));
@@ -557,9 +535,7 @@ int vp_dev_gemm_ln(int epi, const void* A, const void* W, int64_t M, int64_t N, 
     return fail(VP_EINVAL, "epilogue must be 8..12 or 16..19");
   const char* e = gemm_bf16_check((int)M, (int)N, (int)K, K, K);
   if (e) return fail(VP_EINVAL, e);
-  EpiArgs ep;
-  ep.out = out; ep.ldo = N; ep.bias = bias; ep.resid = resid; ep.ldr = N;
-  ep.pos = pos; ep.pos_rows = (int)(pos_rows > 0 ? pos_rows : 1); ep.rowpad = rowpad;
+  EpiArgs ep = epi_args(out, N, bias, resid, N, pos, pos_rows > 0 ? pos_rows : 1, rowpad);
   ep.ln_rs = ln_rs; ep.ln_c = ln_c; ep.st_part = st_part; ep.st_rows = M;
   VP_HIP(gemm_bf16_w4(epi, (const bf16_t*)A, K, (const bf16_t*)W, K, (int)M, (int)N, (int)K, ep,
                       static_cast<hipStream_t>(stream)));
@@ -590,11 +566,9 @@ int vp_dev_gemm_tattn(int which, const void* A, const void* W, int64_t M, int64_
   const int64_t N = which == 0 ? 2 * K : K;
   const char* e = gemm_bf16_check((int)M, (int)N, (int)K, K, K);
   if (e) return fail(VP_EINVAL, e);
-  EpiArgs ep;
-  ep.out = out; ep.ldo = K; ep.bias = bias; ep.ln_rs = ln_rs; ep.ln_c = ln_c; ep.resid = p;
-  ep.cap = cap; ep.heads = (int)heads;
-  ep.cap_c1 = 2.0f * 1.4426950408889634f / cap;
-  ep.cap_c2 = cap * 1.4426950408889634f;
+  EpiArgs ep = epi_args(out, K, bias, p, 0, nullptr, 1, nullptr);
+  ep.ln_rs = ln_rs; ep.ln_c = ln_c;
+  set_tattn_cap(ep, cap, (int)heads);
   VP_HIP(gemm_bf16_w4(which == 0 ? EPI_QK_TATTN_LN : EPI_V_TATTN_LN, (const bf16_t*)A, K, (const bf16_t*)W, K, (int)M,
                       (int)N, (int)K, ep, static_cast<hipStream_t>(stream)));
   return VP_OK;
@@ -608,8 +582,7 @@ int vp_dev_patch_embed(const void* video, int64_t frames, int64_t P, const void*
   using namespace vp;
   if (!video || !wv || !bias || !pos || !out || frames < 1 || N % 256) return fail(VP_EINVAL, "bad argument");
   if (!video_patch_ok((int)P)) return fail(VP_EINVAL, "fused patch embedding needs an even patch size, 4 <= P <= 21");
-  EpiArgs ep;
-  ep.out = out; ep.ldo = N; ep.bias = bias; ep.pos = pos; ep.pos_rows = 256;
+  const EpiArgs ep = epi_args(out, N, bias, nullptr, 0, pos, 256, nullptr);
   VP_HIP(gemm_bf16_w4_video(EPI_POS_BF16, (const bf16_t*)video, (int)P, (const bf16_t*)wv, (int)(frames * 256), (int)N,
                             ep, static_cast<hipStream_t>(stream)));
   return VP_OK;
@@ -625,55 +598,30 @@ int vp_dev_ln_stats(int which, const void* src, int64_t M, int64_t D, float* ln_
   return VP_OK;
 }
 
+// Not in the public header: the kernel (vpi::AttnKernel) choose_attention gives a stack of `kind` (vpi::AttnKind;
+// negative: whatever vp_op_attention makes of S and key paddings), or -1 for a bad argument.  No GPU call.
+int vp_dev_attention_choice(int kind, int precision, int64_t S, float cap, int has_key_pad) {
+  if (kind > ATT_TEXT || (precision != VP_F32 && precision != VP_BF16) || S < 1) return -1;
+  if (kind < 0) kind = op_attention_kind(S, has_key_pad != 0);
+  return choose_attention(kind, precision == VP_BF16, S, cap, has_key_pad != 0);
+}
+
 int vp_op_attention(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S,
                     int64_t heads, float cap, const float* key_pad, void* stream) {
-  using namespace vp;
   if (!qkv || !o || num_seq < 1 || heads < 1) return fail(VP_EINVAL, "bad argument");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (precision == VP_BF16) {
-    if (!fast_cap(cap)) {  // the max-free kernels need 0 < cap <= kMaxFastCap: online softmax
-      if (S < 1) return fail(VP_EINVAL, "bad S");
-      VP_HIP(attention_masked(qkv, o, 1, (int)num_seq, (int)S, (int)heads, cap, key_pad, 0, s));
-    } else if (S == 256)
-      VP_HIP(attention_spatial_bf16((const bf16_t*)qkv, (bf16_t*)o, (int)num_seq, (int)heads, cap, key_pad, s));
-    else if (S > 256 && !key_pad)  // the auxiliary encoder's kernel (any S; a partial last query block)
-      VP_HIP(attention_long_bf16((const bf16_t*)qkv, (bf16_t*)o, (int)num_seq, (int)S, (int)heads, cap, s));
-    else if (S > 256)  // key paddings beyond 256 keys: the forward's choice (run_stack), the generic kernel
-      VP_HIP(attention_masked(qkv, o, 1, (int)num_seq, (int)S, (int)heads, cap, key_pad, 0, s));
-    else if (S >= 1 && S <= 16)
-      VP_HIP(attention_temporal_bf16((const bf16_t*)qkv, (bf16_t*)o, (int)num_seq, (int)S, (int)heads, cap, key_pad, s));
-    else if (S > 16 && S < 256)
-      VP_HIP(attention_seq_bf16((const bf16_t*)qkv, (bf16_t*)o, (int)num_seq, (int)S, (int)heads, cap, key_pad, s));
-    else
-      return fail(VP_EINVAL, "bad S");
-  } else if (precision == VP_F32) {
-    if (S < 1) return fail(VP_EINVAL, "bad S");
-    if (S <= 256) {
-      VP_HIP(attention_f32((const float*)qkv, (float*)o, (int)num_seq, (int)S, (int)heads, cap, key_pad, s));
-    } else {  // the forward's choice for long sequences (run_stack): the MFMA kernel, else online softmax
-      const hipError_t e = attention_f32_mfma((const float*)qkv, (float*)o, (int)num_seq, (int)S, (int)heads, cap,
-                                              key_pad, s);
-      if (e != hipErrorNotSupported) VP_HIP(e);
-      else VP_HIP(attention_masked(qkv, o, 0, (int)num_seq, (int)S, (int)heads, cap, key_pad, 0, s));
-    }
-  } else {
-    return fail(VP_EINVAL, "bad precision");
-  }
+  if (precision != VP_F32 && precision != VP_BF16) return fail(VP_EINVAL, "bad precision");
+  if (S < 1) return fail(VP_EINVAL, "bad S");
+  VP_HIP(launch_attention(op_attention_kind(S, key_pad != nullptr), precision == VP_BF16, qkv, o, (int)num_seq, (int)S,
+                          (int)heads, cap, key_pad, 0, false, static_cast<hipStream_t>(stream)));
   return VP_OK;
 }
 
 int vp_op_attention_masked(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S,
                            int64_t heads, float cap, const float* key_pad, int causal, void* stream) {
-  using namespace vp;
   if (!qkv || !o || num_seq < 1 || heads < 1 || S < 1) return fail(VP_EINVAL, "bad argument");
   if (precision != VP_F32 && precision != VP_BF16) return fail(VP_EINVAL, "bad precision");
-  // the forward's choice (vp_internal.h run_stack, ATT_TEXT): bf16 16 < S <= 256 on the MFMA sequence kernel
-  if (precision == VP_BF16 && fast_cap(cap) && S > 16 && S <= 256)
-    VP_HIP(attention_seq_bf16((const bf16_t*)qkv, (bf16_t*)o, (int)num_seq, (int)S, (int)heads, cap, key_pad,
-                              static_cast<hipStream_t>(stream), causal ? 1 : 0));
-  else
-    VP_HIP(attention_masked(qkv, o, precision == VP_BF16, (int)num_seq, (int)S, (int)heads, cap, key_pad, causal,
-                            static_cast<hipStream_t>(stream)));
+  VP_HIP(launch_attention(ATT_TEXT, precision == VP_BF16, qkv, o, (int)num_seq, (int)S, (int)heads, cap, key_pad,
+                          causal ? 1 : 0, false, static_cast<hipStream_t>(stream)));
   return VP_OK;
 }
 
@@ -703,9 +651,7 @@ int vp_op_patchify(const void* video, int in_dtype, void* patches, int out_dtype
                    int64_t H, int64_t W, int64_t C, int64_t P, int64_t kpad, void* stream) {
   using namespace vp;
   if (!video || !patches || P <= 0) return fail(VP_EINVAL, "bad argument");
-  if (H % P || W % P)
-    return fail(VP_EINVAL, "Image height (" + std::to_string(H) + ") and width (" + std::to_string(W) +
-                               ") should be multiples of patch_size (" + std::to_string(P) + ").");
+  if (H % P || W % P) return fail(VP_EINVAL, patch_size_message(H, W, P));
   if (kpad % 8 || kpad < P * P * C) return fail(VP_EINVAL, "kpad must be >= P*P*C and a multiple of 8");
   if (in_dtype != VP_F32 && in_dtype != VP_BF16 && in_dtype != VP_U8) return fail(VP_EINVAL, "bad dtype");
   VP_HIP(patchify(video, in_dtype, patches, out_dtype == VP_BF16, (int)BT, (int)H, (int)W,

@@ -24,26 +24,87 @@ struct PoolerW {
   int dp = 0;
 };
 
-struct vp_clip {
+// What the two handles that wrap a FactorizedEncoder share: their own leaves (the ParamStore), the wrapped
+// handle and the prefix its leaves carry.  The wrapped encoder's leaves come first in the enumeration.
+struct WrapHandle : vpi::ParamStore {
+  vp_handle* video = nullptr;
+  PoolerW pool;         // the AttenTokenPoolingLayer over the encoder's features
+  int64_t pool_dp = 0;  // its dim_per_head, set by *_create (pool.dp only once packed)
+  bool bf16() const { return video->bf16(); }
+  virtual ~WrapHandle() = default;
+
+  int init(const vp_config* cfg, int dev, const char* prefix) {
+    device = dev;
+    return create_encoder(cfg, dev, prefix, &video);
+  }
+  // every leaf set -> the encoder packed, this handle's device current: the caller packs its own leaves next
+  int begin_finalize() {
+    if (const std::string* n = first_missing()) return fail(VP_ESTATE, "missing parameter: " + *n);
+    int rc = vp_finalize(video);
+    if (rc) return rc;
+    VP_HIP(hipSetDevice(device));
+    return VP_OK;
+  }
+};
+
+namespace {
+
+int wrap_destroy(WrapHandle* w) {
+  if (!w) return VP_OK;
+  vp_destroy(w->video);
+  w->free_all();
+  delete w;
+  return VP_OK;
+}
+
+// a leaf under the wrapped encoder's prefix is the encoder's
+int wrap_set_param(WrapHandle* w, const char* name, const float* data, const int64_t* shape, int ndim) {
+  if (!w) return fail(VP_EINVAL, "null argument");
+  const std::string& px = w->video->prefix;
+  const bool inner = name && !w->finalized && !std::strncmp(name, px.c_str(), px.size());
+  return (inner ? static_cast<ParamStore*>(w->video) : w)->set(name, data, shape, ndim);
+}
+
+int wrap_param_count(const WrapHandle* w, int* count) {
+  if (!w || !count) return fail(VP_EINVAL, "null argument");
+  *count = (int)(w->video->names.size() + w->names.size());
+  return VP_OK;
+}
+
+int wrap_param_name(const WrapHandle* w, int index, const char** name) {
+  if (!w || !name || index < 0) return fail(VP_EINVAL, "bad index");
+  const std::vector<std::string>&inner = w->video->names, &own = w->names;
+  if (index >= (int)(inner.size() + own.size())) return fail(VP_EINVAL, "bad index");
+  *name = (index < (int)inner.size() ? inner[index] : own[index - inner.size()]).c_str();
+  return VP_OK;
+}
+
+int wrap_video_handle(WrapHandle* w, vp_handle** video) {
+  if (!w || !video) return fail(VP_EINVAL, "null argument");
+  *video = w->video;
+  return VP_OK;
+}
+
+}  // namespace
+
+struct vp_clip : WrapHandle {  // 'vision_encoder/' leaves in `video`
   vp_clip_config cfg;
-  int device = 0;
-  bool finalized = false;
-  vp_handle* video = nullptr;  // 'vision_encoder/' leaves
-  std::map<std::string, vpi::HostParam> host;
-  std::vector<std::string> names;
-  std::map<std::string, std::vector<int64_t>> expected;
-  std::vector<vpi::DevBuf> allocs;
-  bool bf16() const { return cfg.video.fprop_dtype == VP_BF16; }
-  std::vector<vpi::LayerW> aux, text;
-  PoolerW pool;  // contrastive_vision_pooler (hidden 4D)
+  std::vector<vpi::LayerW> aux, text;  // `pool`: contrastive_vision_pooler (hidden 4D)
   // text tower: token table [V][D] (fprop dtype), cls [D], sinusoidal table [kMaxTextLen][D]
   void* tok = nullptr;
   float *cls = nullptr, *tpos = nullptr, *uln_g = nullptr, *uln_b = nullptr;
 };
 
+struct vp_classifier : WrapHandle {  // 'encoder/' leaves in `video`
+  vp_config cfg;
+  int num_classes = 0;                       // `pool`: atten_pooler (hidden D)
+  float *wproj = nullptr, *bproj = nullptr;  // projection kernel [D][C] (= Wt of small_gemm), bias [C]
+};
+
 namespace {
 
 struct ClipVideoWs {
+  size_t inner_bytes = 0;  // the wrapped encoder's own workspace, at `inner`
   size_t inner = 0, feat = 0, logits = 0, stats = 0, zpart = 0, z = 0, enc = 0, pooled = 0, total = 0;
 };
 
@@ -56,6 +117,7 @@ ClipVideoWs pool_video_ws(const vp_config& v, int64_t B, int64_t T, int64_t H, i
   const size_t es = v.fprop_dtype == VP_BF16 ? 2 : 4;
   const int64_t gc = std::max<int64_t>(B * vp::pool_chunks((int)(T * N)), B * T * vp::pool_chunks((int)N));
   ClipVideoWs L;
+  L.inner_bytes = inner_bytes;
   size_t off = 0;
   L.inner = off; off = align256(off + inner_bytes);
   L.feat = off; off = align256(off + (size_t)Mp * D * es);
@@ -69,8 +131,13 @@ ClipVideoWs pool_video_ws(const vp_config& v, int64_t B, int64_t T, int64_t H, i
   return L;
 }
 
-ClipVideoWs clip_video_ws(const vp_clip* c, int64_t B, int64_t T, int64_t H, int64_t W, size_t inner_bytes) {
-  return pool_video_ws(c->cfg.video, B, T, H, W, inner_bytes, 4 * c->cfg.video.model_dim / c->cfg.video.num_heads);
+// the layout for a forward over B clips: that of its (largest) chunk
+int pool_video_ws(const WrapHandle* w, int64_t B, int64_t T, int64_t H, int64_t W, ClipVideoWs* L) {
+  size_t inner = 0;
+  int rc = vp_workspace_bytes(w->video, B, T, H, W, &inner);
+  if (rc) return rc;
+  *L = pool_video_ws(w->video->cfg, chunk_of(w->video, B, T, H, W), T, H, W, inner, w->pool_dp);
+  return VP_OK;
 }
 
 struct ClipTextWs {
@@ -98,49 +165,47 @@ ClipTextWs clip_text_ws(const vp_clip* c, int64_t Q, int64_t L) {
 }
 
 // the 12 leaves of an AttenTokenPoolingLayer (layers.py:1044-1136, layers_test.py:283)
-template <class Hd>
-void add_pooler_expected(Hd* c, const std::string& pre, int64_t D, int64_t NH, int64_t dp) {
-  add_expected(c, pre + "pooling_attention_query", {1, D});
-  add_expected(c, pre + "pooling_attention/per_dim_scale/per_dim_scale", {dp});
+void add_pooler_expected(ParamStore& c, const std::string& pre, int64_t D, int64_t NH, int64_t dp) {
+  c.expect(pre + "pooling_attention_query", {1, D});
+  c.expect(pre + "pooling_attention/per_dim_scale/per_dim_scale", {dp});
   for (const char* q : {"query", "key", "value"}) {
-    add_expected(c, pre + "pooling_attention/" + q + "/w", {D, NH, dp});
-    add_expected(c, pre + "pooling_attention/" + q + "/b", {NH, dp});
+    c.expect(pre + "pooling_attention/" + q + "/w", {D, NH, dp});
+    c.expect(pre + "pooling_attention/" + q + "/b", {NH, dp});
   }
-  add_expected(c, pre + "pooling_attention/post/w", {D, NH, dp});
-  add_expected(c, pre + "pooling_attention/post/b", {D});
-  add_expected(c, pre + "pooling_attention_layer_norm/scale", {D});
-  add_expected(c, pre + "pooling_attention_layer_norm/bias", {D});
+  c.expect(pre + "pooling_attention/post/w", {D, NH, dp});
+  c.expect(pre + "pooling_attention/post/b", {D});
+  c.expect(pre + "pooling_attention_layer_norm/scale", {D});
+  c.expect(pre + "pooling_attention_layer_norm/bias", {D});
 }
 
-void build_clip_expected(vp_clip* c) {
-  const vp_clip_config& cc = c->cfg;
-  const int64_t D = cc.video.model_dim, NH = cc.video.num_heads, dp = 4 * D / NH;
+void build_clip_expected(vp_clip& c) {
+  const vp_clip_config& cc = c.cfg;
+  const int64_t D = cc.video.model_dim, NH = cc.video.num_heads;
   if (cc.num_auxiliary_layers > 0)
     add_stack_expected(c, "auxiliary_encoder/transformers_stack/x_layers/", cc.num_auxiliary_layers, D,
                        cc.video.mlp_dim, NH);
-  add_pooler_expected(c, "contrastive_vision_pooler/", D, NH, dp);
-  add_expected(c, "text_encoder/token_emb/emb_var", {(int64_t)cc.vocabulary_size, D});
-  add_expected(c, "text_encoder/cls_emb", {1, 1, D});
+  add_pooler_expected(c, "contrastive_vision_pooler/", D, NH, c.pool_dp);
+  c.expect("text_encoder/token_emb/emb_var", {(int64_t)cc.vocabulary_size, D});
+  c.expect("text_encoder/cls_emb", {1, 1, D});
   add_stack_expected(c, "text_encoder/unimodal_transformer/x_layers/", cc.num_unimodal_layers, D, 4 * D, NH);
-  add_expected(c, "text_encoder/unimodal_ln/scale", {D});
-  add_expected(c, "text_encoder/unimodal_ln/bias", {D});
+  c.expect("text_encoder/unimodal_ln/scale", {D});
+  c.expect("text_encoder/unimodal_ln/bias", {D});
 }
 
 // AttenTokenPoolingLayer (layers.py:1044-1136) with the query folded into the key projection
 // (see clip_kernels.hip): host packing in fp64.
-template <class Hd>
-int pack_pooler(Hd* c, const std::string& root, int64_t D, int64_t H, int64_t dp, PoolerW& pw) {
+int pack_pooler(ParamStore& c, const std::string& root, int64_t D, int64_t H, int64_t dp, PoolerW& pw) {
   const std::string pre = root + "pooling_attention/";
   pw.dp = (int)dp;
-  const auto& query = param_data(c, root + "pooling_attention_query");
-  const auto& wq = param_data(c, pre + "query/w");
-  const auto& bq = param_data(c, pre + "query/b");
-  const auto& wk = param_data(c, pre + "key/w");
-  const auto& wv = param_data(c, pre + "value/w");
-  const auto& bv = param_data(c, pre + "value/b");
-  const auto& wp = param_data(c, pre + "post/w");
-  const auto& bp = param_data(c, pre + "post/b");
-  const auto& pds = param_data(c, pre + "per_dim_scale/per_dim_scale");
+  const auto& query = c.data(root + "pooling_attention_query");
+  const auto& wq = c.data(pre + "query/w");
+  const auto& bq = c.data(pre + "query/b");
+  const auto& wk = c.data(pre + "key/w");
+  const auto& wv = c.data(pre + "value/w");
+  const auto& bv = c.data(pre + "value/b");
+  const auto& wp = c.data(pre + "post/w");
+  const auto& bp = c.data(pre + "post/b");
+  const auto& pds = c.data(pre + "per_dim_scale/per_dim_scale");
   // q~[h][j] = (query . Wq[:, h, j] + bq[h][j]) * 1.442695041/sqrt(dp) * softplus(pds[j])  (:502-527)
   std::vector<double> qt((size_t)H * dp);
   const double r_softplus_0 = 1.442695041 / std::sqrt((double)dp);
@@ -163,7 +228,7 @@ int pack_pooler(Hd* c, const std::string& root, int64_t D, int64_t H, int64_t dp
   for (int64_t n = 0; n < D; ++n)
     for (int64_t k = 0; k < H * dp; ++k) wpt[(size_t)k * D + n] = wp[(size_t)n * H * dp + k];
   std::vector<float> g(D);
-  const auto& sc = param_data(c, root + "pooling_attention_layer_norm/scale");
+  const auto& sc = c.data(root + "pooling_attention_layer_norm/scale");
   for (int64_t d = 0; d < D; ++d) g[d] = sc[d] + 1.0f;
   // bf16 hi/lo split of U for the MFMA logits kernel
   std::vector<uint16_t> ut((size_t)32 * D, 0);
@@ -178,11 +243,10 @@ int pack_pooler(Hd* c, const std::string& root, int64_t D, int64_t H, int64_t dp
       ut[(size_t)(H + h) * D + d] = host_f2bf(u - hf);
     }
   int rc;
-  if ((rc = dev_alloc(c, ut.size() * 2, &pw.Ut))) return rc;
-  VP_HIP(hipMemcpy(pw.Ut, ut.data(), ut.size() * 2, hipMemcpyHostToDevice));
-  if ((rc = upload_f32(c, U, &pw.U)) || (rc = upload_f32(c, wvt, &pw.WvT)) || (rc = upload_f32(c, bv, &pw.bv)) ||
-      (rc = upload_f32(c, wpt, &pw.WpT)) || (rc = upload_f32(c, bp, &pw.bp)) || (rc = upload_f32(c, g, &pw.ln_g)) ||
-      (rc = upload_f32(c, param_data(c, root + "pooling_attention_layer_norm/bias"), &pw.ln_b)))
+  if ((rc = c.upload(ut.data(), ut.size() * 2, &pw.Ut))) return rc;
+  if ((rc = c.upload_f32(U, &pw.U)) || (rc = c.upload_f32(wvt, &pw.WvT)) || (rc = c.upload_f32(bv, &pw.bv)) ||
+      (rc = c.upload_f32(wpt, &pw.WpT)) || (rc = c.upload_f32(bp, &pw.bp)) || (rc = c.upload_f32(g, &pw.ln_g)) ||
+      (rc = c.upload_f32(c.data(root + "pooling_attention_layer_norm/bias"), &pw.ln_b)))
     return rc;
   return VP_OK;
 }
@@ -217,11 +281,46 @@ int run_pooler(Fwd& f, const PoolerW& pw, const void* feat, int M, int G, int Sg
   return VP_OK;
 }
 
+// What clip_video_chunk and classifier_chunk start with, over one chunk of B <= chunk_clips clips: the wrapped
+// encoder's features [B, T*N, D] in the fprop dtype (encoders.py:833-845, :621-630) land in the pooler
+// workspace, a copy goes to spatiotemporal_out if asked, and the pooler's scratch is carved out.
+struct VisionFeat {
+  ClipVideoWs L;
+  void* feat = nullptr;
+  int M = 0;  // B*T*N tokens
+  PoolScratch sc;
+};
+
+int vision_features(WrapHandle* w, const void* video, int in_dtype, int64_t B, int64_t T, int64_t H, int64_t W,
+                    const float* frame_paddings, void* spatial_out, void* spatiotemporal_out, void* workspace,
+                    void* stream, VisionFeat* vf) {
+  ClipVideoWs& L = vf->L;
+  int rc = pool_video_ws(w, B, T, H, W, &L);
+  if (rc) return rc;
+  const vp_config& v = w->video->cfg;
+  const int64_t N = (H / v.patch_size) * (W / v.patch_size), M64 = B * T * N;
+  if (M64 > 0x7fffffff) return fail(VP_ENOTSUP, "too many tokens");
+  vf->M = (int)M64;
+  char* ws = static_cast<char*>(workspace);
+  vf->feat = ws + L.feat;
+  rc = vp_forward(w->video, video, in_dtype, B, T, H, W, frame_paddings, vf->feat, v.fprop_dtype, spatial_out,
+                  ws + L.inner, L.inner_bytes, stream);
+  if (rc) return rc;
+  VP_HIP(hipSetDevice(w->device));
+  if (spatiotemporal_out)
+    VP_HIP(hipMemcpyAsync(spatiotemporal_out, vf->feat, (size_t)M64 * v.model_dim * dtype_bytes(v.fprop_dtype),
+                          hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  vf->sc = PoolScratch{f32(L.logits), f32(L.stats), f32(L.zpart), f32(L.z), f32(L.enc), f32(L.pooled),
+                       (L.z - L.zpart) / 4};
+  return VP_OK;
+}
+
 int pack_text(vp_clip* c) {
   const int64_t D = c->cfg.video.model_dim;
   int rc;
-  if ((rc = upload_mat(c, param_data(c, "text_encoder/token_emb/emb_var"), &c->tok))) return rc;
-  if ((rc = upload_f32(c, param_data(c, "text_encoder/cls_emb"), &c->cls))) return rc;
+  if ((rc = c->upload_mat(c->data("text_encoder/token_emb/emb_var"), c->bf16(), &c->tok))) return rc;
+  if ((rc = c->upload_f32(c->data("text_encoder/cls_emb"), &c->cls))) return rc;
   // PositionalEmbedding (encoders.py:190-224): [sin(t * inv) | cos(t * inv)], zero column for odd D
   std::vector<float> pos((size_t)kMaxTextLen * D, 0.0f);
   const int64_t nts = D / 2;
@@ -232,14 +331,14 @@ int pack_text(vp_clip* c) {
       pos[(size_t)t * D + i] = (float)std::sin(st);
       pos[(size_t)t * D + nts + i] = (float)std::cos(st);
     }
-  if ((rc = upload_f32(c, pos, &c->tpos))) return rc;
+  if ((rc = c->upload_f32(pos, &c->tpos))) return rc;
   std::vector<float> g(D);
-  const auto& sc = param_data(c, "text_encoder/unimodal_ln/scale");
+  const auto& sc = c->data("text_encoder/unimodal_ln/scale");
   for (int64_t d = 0; d < D; ++d) g[d] = sc[d] + 1.0f;
-  if ((rc = upload_f32(c, g, &c->uln_g)) || (rc = upload_f32(c, param_data(c, "text_encoder/unimodal_ln/bias"), &c->uln_b)))
+  if ((rc = c->upload_f32(g, &c->uln_g)) || (rc = c->upload_f32(c->data("text_encoder/unimodal_ln/bias"), &c->uln_b)))
     return rc;
   const int NH = c->cfg.video.num_heads;
-  return pack_stack(c, "text_encoder/unimodal_transformer/x_layers/", c->cfg.num_unimodal_layers, D, 4 * D, NH,
+  return pack_stack(*c, c->bf16(), "text_encoder/unimodal_transformer/x_layers/", c->cfg.num_unimodal_layers, D, 4 * D, NH,
                     false, c->text);
 }
 
@@ -253,108 +352,50 @@ int vp_clip_create(const vp_clip_config* cfg, int device, vp_clip** out) {
   if (cfg->num_auxiliary_layers < 0 || cfg->num_unimodal_layers < 0 || cfg->vocabulary_size < 1)
     return fail(VP_EINVAL, "bad LvT configuration");
   if (cfg->video.num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
-  vp_handle* v = nullptr;
-  int rc = vp_create(&cfg->video, device, &v);
-  if (rc) return rc;
-  v->prefix = "vision_encoder/";
-  v->names.clear();
-  v->expected.clear();
-  build_expected(v);
   vp_clip* c = new vp_clip();
+  int rc = c->init(&cfg->video, device, "vision_encoder/");
+  if (rc) {
+    delete c;
+    return rc;
+  }
   c->cfg = *cfg;
-  c->device = device;
-  c->video = v;
-  build_clip_expected(c);
+  c->pool_dp = 4 * cfg->video.model_dim / cfg->video.num_heads;
+  build_clip_expected(*c);
   *out = c;
   return VP_OK;
 }
 
-int vp_clip_destroy(vp_clip* c) {
-  if (!c) return VP_OK;
-  vp_destroy(c->video);
-  hipSetDevice(c->device);
-  for (auto& a : c->allocs) hipFree(a.p);
-  delete c;
-  return VP_OK;
-}
-
+int vp_clip_destroy(vp_clip* c) { return wrap_destroy(c); }
 int vp_clip_set_param(vp_clip* c, const char* name, const float* host_data, const int64_t* shape, int ndim) {
-  if (!c || !name || !host_data || (ndim > 0 && !shape)) return fail(VP_EINVAL, "null argument");
-  if (c->finalized) return fail(VP_ESTATE, "handle already finalized");
-  if (!std::strncmp(name, "vision_encoder/", 15)) return vp_set_param(c->video, name, host_data, shape, ndim);
-  auto it = c->expected.find(name);
-  if (it == c->expected.end()) return fail(VP_EINVAL, std::string("unexpected parameter: ") + name);
-  const auto& exp = it->second;
-  bool ok = (int)exp.size() == ndim;
-  for (int i = 0; ok && i < ndim; ++i) ok = exp[i] == shape[i];
-  if (!ok) {
-    std::string e = std::string("shape mismatch for ") + name + ": expected (";
-    for (size_t i = 0; i < exp.size(); ++i) e += std::to_string(exp[i]) + (i + 1 < exp.size() ? ", " : "");
-    e += ") got (";
-    for (int i = 0; i < ndim; ++i) e += std::to_string(shape[i]) + (i + 1 < ndim ? ", " : "");
-    return fail(VP_EINVAL, e + ")");
-  }
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  HostParam hp;
-  hp.shape.assign(shape, shape + ndim);
-  hp.data.assign(host_data, host_data + n);
-  c->host[name] = std::move(hp);
-  return VP_OK;
+  return wrap_set_param(c, name, host_data, shape, ndim);
 }
-
-int vp_clip_param_count(const vp_clip* c, int* count) {
-  if (!c || !count) return fail(VP_EINVAL, "null argument");
-  *count = (int)(c->video->names.size() + c->names.size());
-  return VP_OK;
-}
-
-int vp_clip_param_name(const vp_clip* c, int index, const char** name) {
-  if (!c || !name || index < 0) return fail(VP_EINVAL, "bad index");
-  const int nv = (int)c->video->names.size();
-  if (index < nv) {
-    *name = c->video->names[index].c_str();
-    return VP_OK;
-  }
-  if (index - nv >= (int)c->names.size()) return fail(VP_EINVAL, "bad index");
-  *name = c->names[index - nv].c_str();
-  return VP_OK;
-}
+int vp_clip_param_count(const vp_clip* c, int* count) { return wrap_param_count(c, count); }
+int vp_clip_param_name(const vp_clip* c, int index, const char** name) { return wrap_param_name(c, index, name); }
+int vp_clip_video_handle(vp_clip* c, vp_handle** video) { return wrap_video_handle(c, video); }
 
 int vp_clip_finalize(vp_clip* c) {
   if (!c) return fail(VP_EINVAL, "null handle");
   if (c->finalized) return VP_OK;
-  for (const auto& n : c->names)
-    if (!c->host.count(n)) return fail(VP_ESTATE, "missing parameter: " + n);
-  int rc = vp_finalize(c->video);
+  int rc = c->begin_finalize();
   if (rc) return rc;
-  VP_HIP(hipSetDevice(c->device));
   const vp_config& v = c->cfg.video;
   if (c->cfg.num_auxiliary_layers > 0 &&
-      (rc = pack_stack(c, "auxiliary_encoder/transformers_stack/x_layers/", c->cfg.num_auxiliary_layers, v.model_dim,
-                       v.mlp_dim, v.num_heads, c->bf16(), c->aux)))
+      (rc = pack_stack(*c, c->bf16(), "auxiliary_encoder/transformers_stack/x_layers/", c->cfg.num_auxiliary_layers,
+                       v.model_dim, v.mlp_dim, v.num_heads, c->bf16(), c->aux)))
     return rc;
-  if ((rc = pack_pooler(c, "contrastive_vision_pooler/", v.model_dim, v.num_heads, 4 * v.model_dim / v.num_heads,
-                        c->pool)) ||
+  if ((rc = pack_pooler(*c, "contrastive_vision_pooler/", v.model_dim, v.num_heads, c->pool_dp, c->pool)) ||
       (rc = pack_text(c)))
     return rc;
-  c->host.clear();
-  c->finalized = true;
-  return VP_OK;
-}
-
-int vp_clip_video_handle(vp_clip* c, vp_handle** video) {
-  if (!c || !video) return fail(VP_EINVAL, "null argument");
-  *video = c->video;
+  c->seal();
   return VP_OK;
 }
 
 int vp_clip_video_workspace_bytes(const vp_clip* c, int64_t B, int64_t T, int64_t H, int64_t W, size_t* bytes) {
   if (!c || !bytes) return fail(VP_EINVAL, "null argument");
-  size_t inner = 0;
-  int rc = vp_workspace_bytes(c->video, B, T, H, W, &inner);
+  ClipVideoWs L;
+  int rc = pool_video_ws(c, B, T, H, W, &L);
   if (rc) return rc;
-  *bytes = clip_video_ws(c, chunk_of(c->video, B, T, H, W), T, H, W, inner).total;
+  *bytes = L.total;
   return VP_OK;
 }
 
@@ -367,37 +408,25 @@ int clip_video_chunk(vp_clip* c, const void* video, int in_dtype, int64_t B, int
                      const float* frame_paddings, int normalize, float* video_emb, float* frame_emb,
                      void* spatial_out, void* spatiotemporal_out, void* workspace, void* stream) {
   using namespace vp;
-  const bool bf = c->bf16();
-  const int fdt = bf ? VP_BF16 : VP_F32;
-  size_t inner = 0;
-  int rc = vp_workspace_bytes(c->video, B, T, H, W, &inner);
+  // 1. vision encoder -> vision_features [B, T*N, D] (encoders.py:833-845)
+  VisionFeat vf;
+  int rc = vision_features(c, video, in_dtype, B, T, H, W, frame_paddings, spatial_out, spatiotemporal_out, workspace,
+                           stream, &vf);
   if (rc) return rc;
-  const ClipVideoWs L = clip_video_ws(c, B, T, H, W, inner);
-
+  const bool bf = c->bf16();
   const vp_config& v = c->cfg.video;
-  const int P = v.patch_size, N = (int)((H / P) * (W / P)), D = v.model_dim, NH = v.num_heads;
-  const int S = (int)T * N;
-  const int64_t M64 = B * T * N;
-  if (M64 > 0x7fffffff) return fail(VP_ENOTSUP, "too many tokens");
-  const int M = (int)M64;
+  const int D = v.model_dim, NH = v.num_heads, M = vf.M;
+  const int N = (int)(M / (B * T)), S = (int)T * N;
+  void* feat = vf.feat;
   // the auxiliary encoder's GEMM rows: B*T*N padded to the tile (as the vision encoder's, vp_internal.h
   // padded_rows); the padding rows of feat are zeroed, ride through the row-independent GEMM / LayerNorm
   // kernels and are never attended to or pooled (every sequence and pooling group is a block of M rows)
-  const int Mp = (int)padded_rows(c->video, M64);
-  char* ws = static_cast<char*>(workspace);
-  void* feat = ws + L.feat;
+  const int Mp = (int)padded_rows(c->video, M);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // 1. vision encoder -> vision_features [B, T*N, D] (encoders.py:833-845)
-  rc = vp_forward(c->video, video, in_dtype, B, T, H, W, frame_paddings, feat, fdt, spatial_out, ws + L.inner,
-                  inner, stream);
-  if (rc) return rc;
-  VP_HIP(hipSetDevice(c->device));
   const size_t es = bf ? 2 : 4;
-  if (spatiotemporal_out)
-    VP_HIP(hipMemcpyAsync(spatiotemporal_out, feat, (size_t)M * D * es, hipMemcpyDeviceToDevice, s));
   // the vision encoder's scratch regions are free again (stream order): reuse them
   const WsLayout Lv = ws_layout(c->video, B, T, H, W);
-  char* wsv = ws + L.inner;
+  char* wsv = static_cast<char*>(workspace) + vf.L.inner;
   Fwd f;
   f.s = s; f.bf = bf; f.M = Mp; f.D = D; f.NH = NH; f.cap = v.atten_logit_cap;
   f.hb = wsv + Lv.hbuf; f.big = wsv + Lv.big;
@@ -414,15 +443,8 @@ int clip_video_chunk(vp_clip* c, const void* video, int in_dtype, int64_t B, int
     if (rc) return rc;
   }
   // 3. contrastive pooler + L2 (encoders.py:859-872), and per frame (:874-885)
-  float* logits = reinterpret_cast<float*>(ws + L.logits);
-  float* stats = reinterpret_cast<float*>(ws + L.stats);
-  float* zpart = reinterpret_cast<float*>(ws + L.zpart);
-  float* z = reinterpret_cast<float*>(ws + L.z);
-  float* enc = reinterpret_cast<float*>(ws + L.enc);
-  float* pooled = reinterpret_cast<float*>(ws + L.pooled);
-  const PoolScratch sc{logits, stats, zpart, z, enc, pooled, (L.z - L.zpart) / 4};
   auto pool = [&](int G, int Sg, float* dst) -> int {
-    return run_pooler(f, c->pool, feat, M, G, Sg, D, NH, sc, normalize, dst);
+    return run_pooler(f, c->pool, feat, M, G, Sg, D, NH, vf.sc, normalize, dst);
   };
   if ((rc = pool((int)B, S, video_emb))) return rc;
   if (frame_emb && (rc = pool((int)(B * T), N, frame_emb))) return rc;
@@ -439,34 +461,19 @@ int vp_clip_encode_video(vp_clip* c, const void* video, int in_dtype, int64_t B,
                          size_t ws_bytes, void* stream) {
   if (!c || !video || !video_emb || !workspace) return fail(VP_EINVAL, "null argument");
   if (!c->finalized) return fail(VP_ESTATE, "vp_clip_finalize has not been called");
-  const int fdt = c->bf16() ? VP_BF16 : VP_F32;
-  if (spatiotemporal_out && out_dtype != fdt)
-    return fail(VP_EINVAL, "spatiotemporal_features are returned in the fprop dtype");
-  if ((in_dtype != VP_F32 && in_dtype != VP_BF16 && in_dtype != VP_U8) ||
-      (out_dtype != VP_F32 && out_dtype != VP_BF16))
-    return fail(VP_EINVAL, "bad dtype");
-  size_t need = 0;
-  int rc = vp_clip_video_workspace_bytes(c, B, T, H, W, &need);
-  if (rc) return rc;
-  if (ws_bytes < need) return fail(VP_EINVAL, "workspace too small: need " + std::to_string(need));
-  // the batch in chunks of independent clips (vp_internal.h chunk_clips)
-  const int64_t Bc = chunk_of(c->video, B, T, H, W);
-  const vp_config& v = c->cfg.video;
-  const int64_t N = (H / v.patch_size) * (W / v.patch_size), D = v.model_dim;
-  const size_t in_clip = (size_t)(T * H * W * 3) * (in_dtype == VP_U8 ? 1 : in_dtype == VP_BF16 ? 2 : 4);
-  // spatial and spatio-temporal features are written in the fprop dtype (vp_forward's out dtype)
-  const size_t st_clip = (size_t)(T * N * D) * (c->bf16() ? 2 : 4);
-  for (int64_t b0 = 0; b0 < B; b0 += Bc) {
-    const int64_t nb = std::min(Bc, B - b0);
-    rc = clip_video_chunk(c, static_cast<const char*>(video) + b0 * in_clip, in_dtype, nb, T, H, W,
-                          frame_paddings ? frame_paddings + b0 * T : nullptr, normalize, video_emb + b0 * D,
-                          frame_emb ? frame_emb + b0 * T * D : nullptr,
-                          spatial_out ? static_cast<char*>(spatial_out) + b0 * st_clip : nullptr,
-                          spatiotemporal_out ? static_cast<char*>(spatiotemporal_out) + b0 * st_clip : nullptr,
-                          workspace, stream);
-    if (rc) return rc;
-  }
-  return VP_OK;
+  size_t need = 0, st_clip = 0;
+  int rc = check_dtypes(in_dtype, out_dtype, spatiotemporal_out != nullptr, c->video->cfg.fprop_dtype);
+  if (rc || (rc = vp_clip_video_workspace_bytes(c, B, T, H, W, &need)) ||
+      (rc = check_workspace(c->video, T, H, W, ws_bytes, need, c->video->cfg.fprop_dtype, &st_clip)))
+    return rc;
+  const size_t in_clip = video_clip_bytes(T, H, W, in_dtype);
+  const int64_t D = c->cfg.video.model_dim;
+  return for_each_chunk(c->video, B, T, H, W, [&](int64_t b0, int64_t nb) {
+    return clip_video_chunk(c, advance(video, b0 * in_clip), in_dtype, nb, T, H, W, advance(frame_paddings, b0 * T * 4),
+                            normalize, video_emb + b0 * D, advance(frame_emb, b0 * T * D * 4),
+                            advance(spatial_out, b0 * st_clip), advance(spatiotemporal_out, b0 * st_clip), workspace,
+                            stream);
+  });
 }
 
 int vp_clip_text_workspace_bytes(const vp_clip* c, int64_t Q, int64_t L, size_t* bytes) {
@@ -523,21 +530,6 @@ int vp_clip_encode_text(vp_clip* c, const int32_t* ids, const float* paddings, i
 // FactorizedVideoClassifier (encoders.py:583-653): encoder -> AttenTokenPoolingLayer(hidden D,
 // dim_per_head D/heads, paddings None) -> Dense(num_classes)
 // ------------------------------------------------------------------------------------------
-struct vp_classifier {
-  vp_config cfg;
-  int num_classes = 0;
-  int device = 0;
-  bool finalized = false;
-  vp_handle* video = nullptr;  // 'encoder/' leaves
-  std::map<std::string, vpi::HostParam> host;
-  std::vector<std::string> names;
-  std::map<std::string, std::vector<int64_t>> expected;
-  std::vector<vpi::DevBuf> allocs;
-  bool bf16() const { return cfg.fprop_dtype == VP_BF16; }
-  PoolerW pool;                  // atten_pooler
-  float *wproj = nullptr, *bproj = nullptr;  // projection kernel [D][C] (= Wt of small_gemm), bias [C]
-};
-
 extern "C" {
 
 int vp_classifier_create(const vp_config* cfg, int num_classes, int device, vp_classifier** out) {
@@ -545,106 +537,56 @@ int vp_classifier_create(const vp_config* cfg, int num_classes, int device, vp_c
   *out = nullptr;
   if (num_classes < 1) return fail(VP_EINVAL, "num_classes must be positive");
   if (cfg->num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
-  vp_handle* v = nullptr;
-  int rc = vp_create(cfg, device, &v);
-  if (rc) return rc;
-  v->prefix = "encoder/";
-  v->names.clear();
-  v->expected.clear();
-  build_expected(v);
   vp_classifier* c = new vp_classifier();
+  int rc = c->init(cfg, device, "encoder/");
+  if (rc) {
+    delete c;
+    return rc;
+  }
   c->cfg = *cfg;
   c->num_classes = num_classes;
-  c->device = device;
-  c->video = v;
   const int64_t D = cfg->model_dim, NH = cfg->num_heads;
-  add_pooler_expected(c, "atten_pooler/", D, NH, D / NH);
-  add_expected(c, "projection/linear/kernel", {D, (int64_t)num_classes});
-  add_expected(c, "projection/linear/bias", {(int64_t)num_classes});
+  c->pool_dp = D / NH;
+  add_pooler_expected(*c, "atten_pooler/", D, NH, c->pool_dp);
+  c->expect("projection/linear/kernel", {D, (int64_t)num_classes});
+  c->expect("projection/linear/bias", {(int64_t)num_classes});
   *out = c;
   return VP_OK;
 }
 
-int vp_classifier_destroy(vp_classifier* c) {
-  if (!c) return VP_OK;
-  vp_destroy(c->video);
-  hipSetDevice(c->device);
-  for (auto& a : c->allocs) hipFree(a.p);
-  delete c;
-  return VP_OK;
-}
-
+int vp_classifier_destroy(vp_classifier* c) { return wrap_destroy(c); }
 int vp_classifier_set_param(vp_classifier* c, const char* name, const float* host_data, const int64_t* shape,
                             int ndim) {
-  if (!c || !name || !host_data || (ndim > 0 && !shape)) return fail(VP_EINVAL, "null argument");
-  if (c->finalized) return fail(VP_ESTATE, "handle already finalized");
-  if (!std::strncmp(name, "encoder/", 8)) return vp_set_param(c->video, name, host_data, shape, ndim);
-  auto it = c->expected.find(name);
-  if (it == c->expected.end()) return fail(VP_EINVAL, std::string("unexpected parameter: ") + name);
-  const auto& exp = it->second;
-  bool ok = (int)exp.size() == ndim;
-  for (int i = 0; ok && i < ndim; ++i) ok = exp[i] == shape[i];
-  if (!ok) return fail(VP_EINVAL, std::string("shape mismatch for ") + name);
-  size_t n = 1;
-  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  HostParam hp;
-  hp.shape.assign(shape, shape + ndim);
-  hp.data.assign(host_data, host_data + n);
-  c->host[name] = std::move(hp);
-  return VP_OK;
+  return wrap_set_param(c, name, host_data, shape, ndim);
 }
-
-int vp_classifier_param_count(const vp_classifier* c, int* count) {
-  if (!c || !count) return fail(VP_EINVAL, "null argument");
-  *count = (int)(c->video->names.size() + c->names.size());
-  return VP_OK;
-}
-
+int vp_classifier_param_count(const vp_classifier* c, int* count) { return wrap_param_count(c, count); }
 int vp_classifier_param_name(const vp_classifier* c, int index, const char** name) {
-  if (!c || !name || index < 0) return fail(VP_EINVAL, "bad index");
-  const int nv = (int)c->video->names.size();
-  if (index < nv) {
-    *name = c->video->names[index].c_str();
-    return VP_OK;
-  }
-  if (index - nv >= (int)c->names.size()) return fail(VP_EINVAL, "bad index");
-  *name = c->names[index - nv].c_str();
-  return VP_OK;
+  return wrap_param_name(c, index, name);
 }
+int vp_classifier_video_handle(vp_classifier* c, vp_handle** video) { return wrap_video_handle(c, video); }
 
 int vp_classifier_finalize(vp_classifier* c) {
   if (!c) return fail(VP_EINVAL, "null handle");
   if (c->finalized) return VP_OK;
-  for (const auto& n : c->names)
-    if (!c->host.count(n)) return fail(VP_ESTATE, "missing parameter: " + n);
-  int rc = vp_finalize(c->video);
+  int rc = c->begin_finalize();
   if (rc) return rc;
-  VP_HIP(hipSetDevice(c->device));
   const int64_t D = c->cfg.model_dim, NH = c->cfg.num_heads;
-  if ((rc = pack_pooler(c, "atten_pooler/", D, NH, D / NH, c->pool)) ||
-      (rc = upload_f32(c, param_data(c, "projection/linear/kernel"), &c->wproj)) ||
-      (rc = upload_f32(c, param_data(c, "projection/linear/bias"), &c->bproj)))
+  if ((rc = pack_pooler(*c, "atten_pooler/", D, NH, c->pool_dp, c->pool)) ||
+      (rc = c->upload_f32(c->data("projection/linear/kernel"), &c->wproj)) ||
+      (rc = c->upload_f32(c->data("projection/linear/bias"), &c->bproj)))
     return rc;
-  c->host.clear();
-  c->finalized = true;
-  return VP_OK;
-}
-
-int vp_classifier_video_handle(vp_classifier* c, vp_handle** video) {
-  if (!c || !video) return fail(VP_EINVAL, "null argument");
-  *video = c->video;
+  c->seal();
   return VP_OK;
 }
 
 int vp_classifier_workspace_bytes(const vp_classifier* c, int64_t B, int64_t T, int64_t H, int64_t W,
                                   size_t* bytes) {
   if (!c || !bytes) return fail(VP_EINVAL, "null argument");
-  size_t inner = 0;
-  int rc = vp_workspace_bytes(c->video, B, T, H, W, &inner);
+  ClipVideoWs L;
+  int rc = pool_video_ws(c, B, T, H, W, &L);
   if (rc) return rc;
-  const int64_t Bc = chunk_of(c->video, B, T, H, W);
-  const ClipVideoWs L = pool_video_ws(c->cfg, Bc, T, H, W, inner, c->cfg.model_dim / c->cfg.num_heads);
-  *bytes = L.total + align256((size_t)Bc * c->cfg.model_dim * 4);
+  // + the pooled embeddings of one chunk, when the caller does not ask for them
+  *bytes = L.total + align256((size_t)chunk_of(c->video, B, T, H, W) * c->cfg.model_dim * 4);
   return VP_OK;
 }
 
@@ -657,36 +599,20 @@ int classifier_chunk(vp_classifier* c, const void* video, int in_dtype, int64_t 
                      int64_t W, const float* frame_paddings, float* logits, float* embeddings,
                      void* spatial_out, void* spatiotemporal_out, void* workspace, void* stream) {
   using namespace vp;
-  const bool bf = c->bf16();
-  const int fdt = bf ? VP_BF16 : VP_F32;
-  size_t inner = 0;
-  int rc = vp_workspace_bytes(c->video, B, T, H, W, &inner);
+  // 1. encoder -> features [B, T*N, D] (encoders.py:621-630)
+  VisionFeat vf;
+  int rc = vision_features(c, video, in_dtype, B, T, H, W, frame_paddings, spatial_out, spatiotemporal_out, workspace,
+                           stream, &vf);
   if (rc) return rc;
   const vp_config& v = c->cfg;
-  const int D = v.model_dim, NH = v.num_heads;
-  const ClipVideoWs L = pool_video_ws(v, B, T, H, W, inner, D / NH);
-  const int P = v.patch_size, N = (int)((H / P) * (W / P));
-  const int M = (int)(B * T * N);
-  char* ws = static_cast<char*>(workspace);
-  void* feat = ws + L.feat;
+  const int D = v.model_dim, NH = v.num_heads, M = vf.M;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // 1. encoder -> features [B, T*N, D] (encoders.py:621-630)
-  rc = vp_forward(c->video, video, in_dtype, B, T, H, W, frame_paddings, feat, fdt, spatial_out, ws + L.inner,
-                  inner, stream);
-  if (rc) return rc;
-  VP_HIP(hipSetDevice(c->device));
-  if (spatiotemporal_out)
-    VP_HIP(hipMemcpyAsync(spatiotemporal_out, feat, (size_t)M * D * (bf ? 2 : 4), hipMemcpyDeviceToDevice, s));
   Fwd f;
-  f.s = s; f.bf = bf; f.M = M; f.D = D; f.NH = NH; f.cap = v.atten_logit_cap;
+  f.s = s; f.bf = c->bf16(); f.M = M; f.D = D; f.NH = NH; f.cap = v.atten_logit_cap;
   f.pf = &c->video->prof;
   // 2. atten_pooler over all T*N tokens, paddings None (:634-641); 3. projection (:646-652)
-  float* emb = embeddings ? embeddings : reinterpret_cast<float*>(ws + L.total);
-  const PoolScratch sc{reinterpret_cast<float*>(ws + L.logits), reinterpret_cast<float*>(ws + L.stats),
-                       reinterpret_cast<float*>(ws + L.zpart), reinterpret_cast<float*>(ws + L.z),
-                       reinterpret_cast<float*>(ws + L.enc), reinterpret_cast<float*>(ws + L.pooled),
-                       (L.z - L.zpart) / 4};
-  if ((rc = run_pooler(f, c->pool, feat, M, (int)B, (int)(T * N), D, NH, sc, 0, emb))) return rc;
+  float* emb = embeddings ? embeddings : reinterpret_cast<float*>(static_cast<char*>(workspace) + vf.L.total);
+  if ((rc = run_pooler(f, c->pool, vf.feat, M, (int)B, (int)(M / B), D, NH, vf.sc, 0, emb))) return rc;
   VP_HIP(small_gemm(emb, D, 0, c->wproj, 0, c->bproj, 0, logits, c->num_classes, 0, (int)B, c->num_classes, D, 1, s));
   return VP_OK;
 }
@@ -701,31 +627,19 @@ int vp_classifier_forward(vp_classifier* c, const void* video, int in_dtype, int
                           size_t ws_bytes, void* stream) {
   if (!c || !video || !logits || !workspace) return fail(VP_EINVAL, "null argument");
   if (!c->finalized) return fail(VP_ESTATE, "vp_classifier_finalize has not been called");
-  const int fdt = c->bf16() ? VP_BF16 : VP_F32;
-  if (spatiotemporal_out && out_dtype != fdt)
-    return fail(VP_EINVAL, "spatiotemporal_features are returned in the fprop dtype");
-  if ((in_dtype != VP_F32 && in_dtype != VP_BF16 && in_dtype != VP_U8) ||
-      (out_dtype != VP_F32 && out_dtype != VP_BF16))
-    return fail(VP_EINVAL, "bad dtype");
-  size_t need = 0;
-  int rc = vp_classifier_workspace_bytes(c, B, T, H, W, &need);
-  if (rc) return rc;
-  if (ws_bytes < need) return fail(VP_EINVAL, "workspace too small: need " + std::to_string(need));
-  const int64_t Bc = chunk_of(c->video, B, T, H, W);
-  const int64_t N = (H / c->cfg.patch_size) * (W / c->cfg.patch_size), D = c->cfg.model_dim;
-  const size_t in_clip = (size_t)(T * H * W * 3) * (in_dtype == VP_U8 ? 1 : in_dtype == VP_BF16 ? 2 : 4);
-  const size_t st_clip = (size_t)(T * N * D) * (c->bf16() ? 2 : 4);  // features in the fprop dtype
-  for (int64_t b0 = 0; b0 < B; b0 += Bc) {
-    const int64_t nb = std::min(Bc, B - b0);
-    rc = classifier_chunk(c, static_cast<const char*>(video) + b0 * in_clip, in_dtype, nb, T, H, W,
-                          frame_paddings ? frame_paddings + b0 * T : nullptr, logits + b0 * c->num_classes,
-                          embeddings ? embeddings + b0 * D : nullptr,
-                          spatial_out ? static_cast<char*>(spatial_out) + b0 * st_clip : nullptr,
-                          spatiotemporal_out ? static_cast<char*>(spatiotemporal_out) + b0 * st_clip : nullptr,
-                          workspace, stream);
-    if (rc) return rc;
-  }
-  return VP_OK;
+  size_t need = 0, st_clip = 0;
+  int rc = check_dtypes(in_dtype, out_dtype, spatiotemporal_out != nullptr, c->cfg.fprop_dtype);
+  if (rc || (rc = vp_classifier_workspace_bytes(c, B, T, H, W, &need)) ||
+      (rc = check_workspace(c->video, T, H, W, ws_bytes, need, c->video->cfg.fprop_dtype, &st_clip)))
+    return rc;
+  const size_t in_clip = video_clip_bytes(T, H, W, in_dtype);
+  const int64_t D = c->cfg.model_dim;
+  return for_each_chunk(c->video, B, T, H, W, [&](int64_t b0, int64_t nb) {
+    return classifier_chunk(c, advance(video, b0 * in_clip), in_dtype, nb, T, H, W, advance(frame_paddings, b0 * T * 4),
+                            logits + b0 * c->num_classes, advance(embeddings, b0 * D * 4),
+                            advance(spatial_out, b0 * st_clip), advance(spatiotemporal_out, b0 * st_clip), workspace,
+                            stream);
+  });
 }
 
 }  // extern "C"

@@ -16,30 +16,9 @@
 #include <vector>
 
 #include "vp_kernels.h"
+#include "vp_params.h"
 
 namespace vpi {
-
-inline thread_local std::string g_err;
-
-inline int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define VP_HIP(expr)                                                                   \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess)                                                              \
-      return fail(VP_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));        \
-  } while (0)
-
-inline uint16_t host_f2bf(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7F800000u) == 0x7F800000u) return (uint16_t)(u >> 16);  // inf / nan
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
 
 // jax.image.resize(method='bilinear') weights W[in][out] (restated in oracle/ and DESIGN.md:
 // triangle kernel, half-pixel centres, antialiased when downsampling, normalised columns).
@@ -66,16 +45,6 @@ inline std::vector<double> resize_weights(int in_size, int out_size) {
   }
   return w;
 }
-
-struct HostParam {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
 
 struct LayerW {  // one transformer layer, packed
   void* wqkv = nullptr;  // [3D][D]   rows (q|k|v, head, dh); q rows scaled by dh^-0.5
@@ -134,16 +103,10 @@ struct Profiler {
 
 }  // namespace
 
-struct vp_handle {
+struct vp_handle : vpi::ParamStore {
   vp_config cfg;
-  int device = 0;
-  std::string prefix;  // "" for a FactorizedEncoder, "vision_encoder/" inside a vp_clip
+  std::string prefix;  // "" for a FactorizedEncoder, "vision_encoder/" inside a vp_clip, "encoder/" inside a vp_classifier
   bool bf16() const { return cfg.fprop_dtype == VP_BF16; }
-  bool finalized = false;
-  std::map<std::string, vpi::HostParam> host;
-  std::vector<std::string> names;
-  std::map<std::string, std::vector<int64_t>> expected;
-  std::vector<vpi::DevBuf> allocs;
   // packed device weights
   int kpad = 0;
   void* wpatch = nullptr;      // [D][kpad]
@@ -164,95 +127,28 @@ namespace vpi {
 
 inline bool is_bf16(const vp_handle* h) { return h->bf16(); }
 
-// device buffers owned by a handle (vp_handle or vp_clip: members allocs, bf16())
-template <class H>
-int dev_alloc(H* h, size_t bytes, void** out) {
-  void* p = nullptr;
-  if (hipMalloc(&p, bytes) != hipSuccess) return fail(VP_ENOMEM, "hipMalloc failed");
-  h->allocs.push_back({p, bytes});
-  *out = p;
-  return VP_OK;
-}
-
-template <class H>
-int upload_f32(H* h, const std::vector<float>& v, float** out) {
-  void* p;
-  int rc = dev_alloc(h, v.size() * 4, &p);
-  if (rc) return rc;
-  VP_HIP(hipMemcpy(p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-  *out = static_cast<float*>(p);
-  return VP_OK;
-}
-
-// matrix in the handle's compute dtype
-template <class H>
-int upload_mat(H* h, const std::vector<float>& v, void** out) {
-  if (!h->bf16()) {
-    float* p;
-    int rc = upload_f32(h, v, &p);
-    *out = p;
-    return rc;
-  }
-  std::vector<uint16_t> b(v.size());
-  for (size_t i = 0; i < v.size(); ++i) b[i] = host_f2bf(v[i]);
-  void* p;
-  int rc = dev_alloc(h, b.size() * 2, &p);
-  if (rc) return rc;
-  VP_HIP(hipMemcpy(p, b.data(), b.size() * 2, hipMemcpyHostToDevice));
-  *out = p;
-  return VP_OK;
-}
-
-template <class H>
-void add_expected(H* h, const std::string& n, std::vector<int64_t> s) {
-  h->names.push_back(n);
-  h->expected[n] = std::move(s);
-}
-
 // the 16 leaves of a scanned StackedTransformer (layers.py:940-1041) under `pre` (".../x_layers/")
-template <class H>
-void add_stack_expected(H* h, const std::string& pre, int64_t L, int64_t D, int64_t F, int64_t NH) {
+inline void add_stack_expected(ParamStore& ps, const std::string& pre, int64_t L, int64_t D, int64_t F, int64_t NH) {
   const int64_t DH = D / NH;
-  add_expected(h, pre + "layer_norm/scale", {L, D});
-  add_expected(h, pre + "layer_norm/bias", {L, D});
+  ps.expect(pre + "layer_norm/scale", {L, D});
+  ps.expect(pre + "layer_norm/bias", {L, D});
   for (const char* qkv : {"query", "key", "value"}) {
-    add_expected(h, pre + "self_attention/" + qkv + "/w", {L, D, NH, DH});
-    add_expected(h, pre + "self_attention/" + qkv + "/b", {L, NH, DH});
+    ps.expect(pre + "self_attention/" + qkv + "/w", {L, D, NH, DH});
+    ps.expect(pre + "self_attention/" + qkv + "/b", {L, NH, DH});
   }
-  add_expected(h, pre + "self_attention/post/w", {L, D, NH, DH});
-  add_expected(h, pre + "self_attention/post/b", {L, D});
-  add_expected(h, pre + "ff_layer/layer_norm/scale", {L, D});
-  add_expected(h, pre + "ff_layer/layer_norm/bias", {L, D});
-  add_expected(h, pre + "ff_layer/ffn_layer1/linear/kernel", {L, D, F});
-  add_expected(h, pre + "ff_layer/ffn_layer1/linear/bias", {L, F});
-  add_expected(h, pre + "ff_layer/ffn_layer2/linear/kernel", {L, F, D});
-  add_expected(h, pre + "ff_layer/ffn_layer2/linear/bias", {L, D});
+  ps.expect(pre + "self_attention/post/w", {L, D, NH, DH});
+  ps.expect(pre + "self_attention/post/b", {L, D});
+  ps.expect(pre + "ff_layer/layer_norm/scale", {L, D});
+  ps.expect(pre + "ff_layer/layer_norm/bias", {L, D});
+  ps.expect(pre + "ff_layer/ffn_layer1/linear/kernel", {L, D, F});
+  ps.expect(pre + "ff_layer/ffn_layer1/linear/bias", {L, F});
+  ps.expect(pre + "ff_layer/ffn_layer2/linear/kernel", {L, F, D});
+  ps.expect(pre + "ff_layer/ffn_layer2/linear/bias", {L, D});
 }
 
-inline void build_expected(vp_handle* h) {
-  const vp_config& c = h->cfg;
-  const int64_t D = c.model_dim, F = c.mlp_dim, NH = c.num_heads;
-  const int64_t P = c.patch_size;
-  const std::string& px = h->prefix;
-  add_expected(h, px + "patch_projection/linear/kernel", {P * P * 3, D});
-  add_expected(h, px + "patch_projection/linear/bias", {D});
-  add_expected(h, px + "spatial_pos_emb/emb_var", {(int64_t)c.pos_emb_h * c.pos_emb_w, D});
-  const char* stacks[2] = {"spatial_encoder", "temporal_encoder"};
-  const int64_t Ls[2] = {c.num_spatial_layers, c.num_temporal_layers};
-  for (int s = 0; s < 2; ++s) {
-    add_stack_expected(h, px + stacks[s] + "/transformers_stack/x_layers/", Ls[s], D, F, NH);
-    if (s == 0) {
-      add_expected(h, px + "spatial_ln/scale", {D});
-      add_expected(h, px + "spatial_ln/bias", {D});
-      add_expected(h, px + "temporal_pos_emb/emb_var", {(int64_t)c.pos_emb_t, D});
-    }
-  }
-  add_expected(h, px + "temporal_ln/scale", {D});
-  add_expected(h, px + "temporal_ln/bias", {D});
-}
-
-template <class H>
-const std::vector<float>& param_data(H* h, const std::string& n) { return h->host.at(n).data; }
+// A FactorizedEncoder handle whose leaves are named under `prefix` (vp_abi.cpp): vp_create's own with "",
+// the encoder wrapped by a vp_clip / vp_classifier with theirs.
+int create_encoder(const vp_config* cfg, int device, const std::string& prefix, vp_handle** out);
 
 // LayerNorm folded into the following GEMM (bf16 handles): w [N][K] *= gamma[k],
 // b[n] += sum_k w[n][k] beta[k] (before scaling, fp64), c[n] = sum_k bf16(w'[n][k]) (fp64).
@@ -289,27 +185,26 @@ enum QkvExtra {
 // the consuming GEMMs (bf16 handles, EPI_*_LN); otherwise W / b are the plain projections and the
 // LayerNorms run as kernels (ln*_g / ln*_b).  The row-major q|k|v copy is always kept: it serves the
 // unfused attention paths (other patch grids, frame paddings, caps outside the fast range).
-template <class H>
-int pack_stack(H* h, const std::string& pre, int L, int64_t D, int64_t F, int NH, bool fold,
-               std::vector<LayerW>& out, QkvExtra extra = QKV_PLAIN) {
+inline int pack_stack(ParamStore& ps, bool bf16, const std::string& pre, int L, int64_t D, int64_t F, int NH, bool fold,
+                      std::vector<LayerW>& out, QkvExtra extra = QKV_PLAIN) {
   const bool qk_perm = extra == QKV_PER_HEAD;
   const float qscale = 1.0f / std::sqrt((float)(D / NH));  // layers.py:576-583
-  const auto& lng = param_data(h, pre + "layer_norm/scale");
-  const auto& lnb = param_data(h, pre + "layer_norm/bias");
-  const auto& ln2g = param_data(h, pre + "ff_layer/layer_norm/scale");
-  const auto& ln2b = param_data(h, pre + "ff_layer/layer_norm/bias");
-  const std::vector<float>* wq[3] = {&param_data(h, pre + "self_attention/query/w"),
-                                     &param_data(h, pre + "self_attention/key/w"),
-                                     &param_data(h, pre + "self_attention/value/w")};
-  const std::vector<float>* bq[3] = {&param_data(h, pre + "self_attention/query/b"),
-                                     &param_data(h, pre + "self_attention/key/b"),
-                                     &param_data(h, pre + "self_attention/value/b")};
-  const auto& wpost = param_data(h, pre + "self_attention/post/w");
-  const auto& bpost = param_data(h, pre + "self_attention/post/b");
-  const auto& w1 = param_data(h, pre + "ff_layer/ffn_layer1/linear/kernel");
-  const auto& b1 = param_data(h, pre + "ff_layer/ffn_layer1/linear/bias");
-  const auto& w2 = param_data(h, pre + "ff_layer/ffn_layer2/linear/kernel");
-  const auto& b2 = param_data(h, pre + "ff_layer/ffn_layer2/linear/bias");
+  const auto& lng = ps.data(pre + "layer_norm/scale");
+  const auto& lnb = ps.data(pre + "layer_norm/bias");
+  const auto& ln2g = ps.data(pre + "ff_layer/layer_norm/scale");
+  const auto& ln2b = ps.data(pre + "ff_layer/layer_norm/bias");
+  const std::vector<float>* wq[3] = {&ps.data(pre + "self_attention/query/w"),
+                                     &ps.data(pre + "self_attention/key/w"),
+                                     &ps.data(pre + "self_attention/value/w")};
+  const std::vector<float>* bq[3] = {&ps.data(pre + "self_attention/query/b"),
+                                     &ps.data(pre + "self_attention/key/b"),
+                                     &ps.data(pre + "self_attention/value/b")};
+  const auto& wpost = ps.data(pre + "self_attention/post/w");
+  const auto& bpost = ps.data(pre + "self_attention/post/b");
+  const auto& w1 = ps.data(pre + "ff_layer/ffn_layer1/linear/kernel");
+  const auto& b1 = ps.data(pre + "ff_layer/ffn_layer1/linear/bias");
+  const auto& w2 = ps.data(pre + "ff_layer/ffn_layer2/linear/kernel");
+  const auto& b2 = ps.data(pre + "ff_layer/ffn_layer2/linear/bias");
   out.resize(L);
   for (int l = 0; l < L; ++l) {
     LayerW& lw = out[l];
@@ -332,7 +227,7 @@ int pack_stack(H* h, const std::string& pre, int L, int64_t D, int64_t F, int NH
     }
     if (fold) {
       const std::vector<float> c = fold_ln(t, tb, g1, be1, 3 * D, D);
-      if ((rc = upload_f32(h, c, &lw.cqkv))) return rc;
+      if ((rc = ps.upload_f32(c, &lw.cqkv))) return rc;
       if (extra == QKV_BLOCKED && (3 * D) % 256 == 0) {  // the row-blocked copy (LayerW::wqkv_blk)
         const int64_t N3 = 3 * D;
         std::vector<float> pt((size_t)N3 * D), pb(N3), pc(N3);
@@ -342,8 +237,8 @@ int pack_stack(H* h, const std::string& pre, int L, int64_t D, int64_t F, int NH
           pb[r] = tb[src];
           pc[r] = c[src];
         }
-        if ((rc = upload_mat(h, pt, &lw.wqkv_blk)) || (rc = upload_f32(h, pb, &lw.bqkv_blk)) ||
-            (rc = upload_f32(h, pc, &lw.cqkv_blk)))
+        if ((rc = ps.upload_mat(pt, bf16, &lw.wqkv_blk)) || (rc = ps.upload_f32(pb, &lw.bqkv_blk)) ||
+            (rc = ps.upload_f32(pc, &lw.cqkv_blk)))
           return rc;
       }
       if (qk_perm) {  // [q_h | k_h] per head (rows of the folded t, b', c)
@@ -357,18 +252,18 @@ int pack_stack(H* h, const std::string& pre, int L, int64_t D, int64_t F, int NH
               bq[dst] = tb[src];
               cq[dst] = c[src];
             }
-        if ((rc = upload_mat(h, tq, &lw.wqk)) || (rc = upload_f32(h, bq, &lw.bqk)) ||
-            (rc = upload_f32(h, cq, &lw.cqk)))
+        if ((rc = ps.upload_mat(tq, bf16, &lw.wqk)) || (rc = ps.upload_f32(bq, &lw.bqk)) ||
+            (rc = ps.upload_f32(cq, &lw.cqk)))
           return rc;
       }
     }
-    if ((rc = upload_mat(h, t, &lw.wqkv)) || (rc = upload_f32(h, tb, &lw.bqkv))) return rc;
+    if ((rc = ps.upload_mat(t, bf16, &lw.wqkv)) || (rc = ps.upload_f32(tb, &lw.bqkv))) return rc;
     // post: w[d][n][h] is already [out D][in N*H]
     std::vector<float> wp(wpost.begin() + (size_t)l * D * D, wpost.begin() + (size_t)(l + 1) * D * D);
     std::vector<float> bp(bpost.begin() + (size_t)l * D, bpost.begin() + (size_t)(l + 1) * D);
-    if ((rc = upload_mat(h, wp, &lw.wpost)) || (rc = upload_f32(h, bp, &lw.bpost))) return rc;
-    if ((rc = upload_f32(h, g1, &lw.ln1_g)) || (rc = upload_f32(h, be1, &lw.ln1_b)) ||
-        (rc = upload_f32(h, g2, &lw.ln2_g)) || (rc = upload_f32(h, be2, &lw.ln2_b)))
+    if ((rc = ps.upload_mat(wp, bf16, &lw.wpost)) || (rc = ps.upload_f32(bp, &lw.bpost))) return rc;
+    if ((rc = ps.upload_f32(g1, &lw.ln1_g)) || (rc = ps.upload_f32(be1, &lw.ln1_b)) ||
+        (rc = ps.upload_f32(g2, &lw.ln2_g)) || (rc = ps.upload_f32(be2, &lw.ln2_b)))
       return rc;
     std::vector<float> t1((size_t)F * D), t2((size_t)D * F);
     const float* w1l = w1.data() + (size_t)l * D * F;  // [D][F]
@@ -394,10 +289,10 @@ int pack_stack(H* h, const std::string& pre, int L, int64_t D, int64_t F, int NH
         c.swap(pc);
         lw.ffn_blk = true;
       }
-      if ((rc = upload_f32(h, c, &lw.c1))) return rc;
+      if ((rc = ps.upload_f32(c, &lw.c1))) return rc;
     }
-    if ((rc = upload_mat(h, t1, &lw.w1)) || (rc = upload_f32(h, bb1, &lw.b1)) ||
-        (rc = upload_mat(h, t2, &lw.w2)) || (rc = upload_f32(h, bb2, &lw.b2)))
+    if ((rc = ps.upload_mat(t1, bf16, &lw.w1)) || (rc = ps.upload_f32(bb1, &lw.b1)) ||
+        (rc = ps.upload_mat(t2, bf16, &lw.w2)) || (rc = ps.upload_f32(bb2, &lw.b2)))
       return rc;
   }
   return VP_OK;
@@ -456,13 +351,17 @@ inline int64_t chunk_clips(const vp_config& c, int64_t T, int64_t H, int64_t W) 
   return tok > 0 ? std::max<int64_t>(1, max_rows / tok) : 1;
 }
 
+// the reference's message for frames the patch grid does not divide (encoders.py:86-89)
+inline std::string patch_size_message(int64_t H, int64_t W, int64_t P) {
+  return "Image height (" + std::to_string(H) + ") and width (" + std::to_string(W) +
+         ") should be multiples of patch_size (" + std::to_string(P) + ").";
+}
+
 inline int check_geometry(const vp_handle* h, int64_t B, int64_t T, int64_t H, int64_t W) {
   const int64_t P = h->cfg.patch_size;
   if (B < 1 || T < 1 || H < 1 || W < 1) return fail(VP_EINVAL, "inputs must be [B, T, H, W, 3] with positive sizes");
   if (H != W) return fail(VP_EINVAL, "assert h == w failed (encoders.py:435)");
-  if (H % P || W % P)
-    return fail(VP_EINVAL, "Image height (" + std::to_string(H) + ") and width (" + std::to_string(W) +
-                               ") should be multiples of patch_size (" + std::to_string(P) + ").");
+  if (H % P || W % P) return fail(VP_EINVAL, patch_size_message(H, W, P));
   if (T * (H / P) * (W / P) > ((int64_t)1 << 30))
     return fail(VP_EINVAL, "one clip of " + std::to_string(T) + "x" + std::to_string(H) + "x" + std::to_string(W) +
                                " has more than 2^30 tokens (32-bit row indices)");
@@ -474,9 +373,61 @@ inline int64_t chunk_of(const vp_handle* h, int64_t B, int64_t T, int64_t H, int
   return std::min<int64_t>(B, chunk_clips(h->cfg, T, H, W));
 }
 
-}  // namespace
+inline size_t dtype_bytes(int dtype) { return dtype == VP_U8 ? 1 : dtype == VP_BF16 ? 2 : 4; }
 
-namespace vpi {
+// dtype codes of a forward entry point; spatiotemporal features are the encoder's output itself, so they
+// come in the handle's fprop dtype only
+inline int check_dtypes(int in_dtype, int out_dtype, bool spatiotemporal_out, int fprop_dtype) {
+  if (spatiotemporal_out && out_dtype != fprop_dtype)
+    return fail(VP_EINVAL, "spatiotemporal_features are returned in the fprop dtype");
+  if ((in_dtype != VP_F32 && in_dtype != VP_BF16 && in_dtype != VP_U8) || (out_dtype != VP_F32 && out_dtype != VP_BF16))
+    return fail(VP_EINVAL, "bad dtype");
+  return VP_OK;
+}
+
+// bytes of one clip of the caller's frames
+inline size_t video_clip_bytes(int64_t T, int64_t H, int64_t W, int in_dtype) {
+  return (size_t)(T * H * W * 3) * dtype_bytes(in_dtype);
+}
+
+// the caller's workspace against `need`; *feat_clip: bytes of one clip of features [T*N][D] in feat_dtype
+inline int check_workspace(const vp_handle* h, int64_t T, int64_t H, int64_t W, size_t ws_bytes, size_t need,
+                           int feat_dtype, size_t* feat_clip) {
+  if (ws_bytes < need) return fail(VP_EINVAL, "workspace too small: need " + std::to_string(need));
+  const int64_t P = h->cfg.patch_size;
+  *feat_clip = (size_t)(T * (H / P) * (W / P) * h->cfg.model_dim) * dtype_bytes(feat_dtype);
+  return VP_OK;
+}
+
+// fn(b0, nb) over B clips in consecutive chunks of at most chunk_of(...) clips; stops at the first error
+template <class Fn>
+int for_each_chunk(const vp_handle* h, int64_t B, int64_t T, int64_t H, int64_t W, Fn&& fn) {
+  const int64_t Bc = chunk_of(h, B, T, H, W);
+  for (int64_t b0 = 0; b0 < B; b0 += Bc) {
+    const int rc = fn(b0, std::min(Bc, B - b0));
+    if (rc) return rc;
+  }
+  return VP_OK;
+}
+
+// a caller's buffer `bytes` further on; an absent (null) buffer stays absent
+template <class T>
+T* advance(T* p, size_t bytes) {
+  return p ? reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + bytes) : nullptr;
+}
+
+// algorithmic bytes of a GEMM [M][K] . [N][K]^T with es-byte operands (the profiler's roofline input)
+inline double gemm_bytes(double M, double K, double N, double es, double out_bytes, double resid_bytes) {
+  return M * K * es + N * K * es + M * N * out_bytes + M * N * resid_bytes;
+}
+
+inline vp::EpiArgs epi_args(void* out, int64_t ldo, const float* bias, const void* resid, int64_t ldr, const float* pos,
+                            int64_t pos_rows, const float* rowpad) {
+  vp::EpiArgs ep;
+  ep.out = out; ep.ldo = ldo; ep.bias = bias; ep.resid = resid; ep.ldr = ldr;
+  ep.pos = pos; ep.pos_rows = (int)pos_rows; ep.rowpad = rowpad;
+  return ep;
+}
 
 // The bf16 attention kernels compute the capped softmax without a running max: every numerator
 // is exp(l) with |l| <= cap, and both the row sum and the unnormalised O = sum_s exp(l_s) v_s are
@@ -489,12 +440,71 @@ namespace vpi {
 constexpr float kMaxFastCap = 50.0f;
 inline bool fast_cap(float cap) { return cap > 0.0f && cap <= kMaxFastCap; }
 
-// which attention kernel a stack uses (the rest of the pre-LN layer is shared)
+// what a stack's attention is for (the rest of the pre-LN layer is shared); choose_attention picks the kernel
 enum AttnKind {
-  ATT_VIDEO = 0,  // factorized encoder: S == 256 spatial / S <= 16 temporal (bf16), any S <= 256 (fp32)
+  ATT_VIDEO = 0,  // factorized encoder: spatial (S = the patch grid) and temporal (S = T) stacks, key paddings
   ATT_LONG = 1,   // auxiliary encoder over T*N tokens, no masks
   ATT_TEXT = 2,   // text tower: causal + key paddings (layers.py:155-179)
 };
+
+// the attention kernels (vp_kernels.h)
+enum AttnKernel {
+  ATTN_SPATIAL = 0,   // attention_spatial_bf16: S == 256
+  ATTN_TEMPORAL = 1,  // attention_temporal_bf16: S <= 16
+  ATTN_SEQ = 2,       // attention_seq_bf16: 16 < S <= 256, optionally causal
+  ATTN_LONG = 3,      // attention_long_bf16: any S, no masks
+  ATTN_MASKED = 4,    // attention_masked: online softmax, any S, cap, masks and dtype
+  ATTN_F32 = 5,       // attention_f32: S <= 256
+  ATTN_F32_MFMA = 6,  // attention_f32_mfma: any S, 0 < cap <= kMaxFastCap
+};
+
+// The one choice of attention kernel: the forward (run_stack) and the op-level entry points (vp_op_attention*,
+// which the kernel parity tests call) all come through here.  Every kernel but ATTN_MASKED and ATTN_F32 has the
+// max-free softmax only, hence fast_cap.  No tier depends on key paddings: ATT_LONG has none by contract and
+// every kernel an ATT_VIDEO / ATT_TEXT stack can get takes them.
+inline AttnKernel choose_attention(int kind, bool bf16, int64_t S, float cap, bool /*has_key_pad*/) {
+  const bool fast = fast_cap(cap);
+  if (kind == ATT_TEXT) return bf16 && fast && S > 16 && S <= 256 ? ATTN_SEQ : ATTN_MASKED;
+  if (bf16 && !fast) return ATTN_MASKED;
+  if (kind == ATT_LONG) {
+    if (!bf16) return fast ? ATTN_F32_MFMA : ATTN_MASKED;
+    return S >= 256 ? ATTN_LONG : S > 16 ? ATTN_SEQ : ATTN_TEMPORAL;
+  }
+  if (!bf16) return S <= 256 ? ATTN_F32 : fast ? ATTN_F32_MFMA : ATTN_MASKED;
+  return S == 256 ? ATTN_SPATIAL : S <= 16 ? ATTN_TEMPORAL : S < 256 ? ATTN_SEQ : ATTN_MASKED;
+}
+
+// vp_op_attention has no kind: sequences past 256 keys without paddings are the auxiliary encoder's
+inline int op_attention_kind(int64_t S, bool has_key_pad) { return S > 256 && !has_key_pad ? ATT_LONG : ATT_VIDEO; }
+
+// Launches choose_attention's kernel over qkv [num_seq * S][3 * heads * 64] -> o.  ATT_LONG passes no key
+// paddings, only ATT_TEXT a causal mask; blk: q|k|v in the row-blocked layout (ATTN_SPATIAL only).
+inline hipError_t launch_attention(int kind, bool bf16, const void* qkv, void* o, int num_seq, int S, int heads, float cap,
+                                   const float* key_pad, int causal, bool blk, hipStream_t s) {
+  using namespace vp;
+  if (kind == ATT_LONG) key_pad = nullptr;
+  if (kind != ATT_TEXT) causal = 0;
+  const bf16_t* qb = static_cast<const bf16_t*>(qkv);
+  bf16_t* ob = static_cast<bf16_t*>(o);
+  switch (choose_attention(kind, bf16, S, cap, key_pad != nullptr)) {
+    case ATTN_SPATIAL: return attention_spatial_bf16(qb, ob, num_seq, heads, cap, key_pad, s, blk);
+    case ATTN_TEMPORAL: return attention_temporal_bf16(qb, ob, num_seq, S, heads, cap, key_pad, s);
+    case ATTN_SEQ: return attention_seq_bf16(qb, ob, num_seq, S, heads, cap, key_pad, s, causal);
+    case ATTN_LONG: return attention_long_bf16(qb, ob, num_seq, S, heads, cap, s);
+    case ATTN_MASKED: return attention_masked(qkv, o, bf16, num_seq, S, heads, cap, key_pad, causal, s);
+    case ATTN_F32: return attention_f32((const float*)qkv, (float*)o, num_seq, S, heads, cap, key_pad, s);
+    case ATTN_F32_MFMA: return attention_f32_mfma((const float*)qkv, (float*)o, num_seq, S, heads, cap, key_pad, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+// the fused temporal attention's cap arguments (EPI_*_TATTN_LN): cap_c1 / cap_c2 are the capped-exp constants
+// 2 log2(e) / cap and cap log2(e), the same IEEE division the unfused kernels do on the device
+inline void set_tattn_cap(vp::EpiArgs& ep, float cap, int heads) {
+  ep.cap = cap; ep.heads = heads;
+  ep.cap_c1 = 2.0f * 1.4426950408889634f / cap;
+  ep.cap_c2 = cap * 1.4426950408889634f;
+}
 
 // One forward pass's launch context: stream, dtype, row count, scratch buffers and the profiler.
 // hipEventRecord on `s`; inside a stream capture an event-record node of the graph instead (a
@@ -551,9 +561,7 @@ struct Fwd {
   hipError_t gemm(int epi, const void* A, int K, const void* Wt, int N, void* o, int64_t ldo, const float* bias,
                   const void* resid, const float* pos, int pos_rows, const float* rowpad,
                   const float* lnc = nullptr) const {
-    vp::EpiArgs ep;
-    ep.out = o; ep.ldo = ldo; ep.bias = bias; ep.resid = resid; ep.ldr = ldo;
-    ep.pos = pos; ep.pos_rows = pos_rows; ep.rowpad = rowpad;
+    vp::EpiArgs ep = epi_args(o, ldo, bias, resid, ldo, pos, pos_rows, rowpad);
     ep.ln_rs = ln_rs; ep.ln_c = lnc; ep.st_part = st_part; ep.st_rows = M;
     if (bf && small_m) {
       // the text tower's rows are padded to 64 only (clip_text_ws): the 256-row kernels cannot take
@@ -578,9 +586,7 @@ struct Fwd {
                 int kind, bool fold, bool relu) {
     using namespace vp;
     const double dM = M, dD = D, dF = F, dE = bf ? 2.0 : 4.0;
-    auto gbytes = [&](double K, double N, double outb, double resid) {  // algorithmic GEMM bytes
-      return dM * K * dE + N * K * dE + dM * N * outb + dM * N * resid;
-    };
+    auto gbytes = [&](double K, double N, double outb, double resid) { return gemm_bytes(dM, K, N, dE, outb, resid); };
     const double aflops = 4.0 * num_seq * (double)S * S * dD;
     const double abytes = dM * 3 * dD * dE + dM * dD * dE;
     const double ln_bytes = 2.0 * dM * dD * dE;
@@ -600,16 +606,14 @@ struct Fwd {
       if (tattn) {
         // P (normalised bf16 probabilities, 512 B per (sequence, head)) goes to `big`; O to hb
         vp::EpiArgs ep;
-        ep.ln_rs = ln_rs; ep.cap = cap; ep.heads = NH;
-        ep.cap_c1 = 2.0f * 1.4426950408889634f / cap;  // the same IEEE division the kernel did
-        ep.cap_c2 = cap * 1.4426950408889634f;
-        ep.out = big; ep.bias = lw.bqk; ep.ln_c = lw.cqk;
+        set_tattn_cap(ep, cap, NH);
+        ep.ln_rs = ln_rs; ep.out = big; ep.bias = lw.bqk; ep.ln_c = lw.cqk;
         VP_HIP(rec(PC_GEMM_QKV_TATTN, 2.0 * dM * dD * 2 * dD + 4.0 * num_seq * (double)S * S * dD,
                    gbytes(dD, 2 * dD, 0, 0) + dM * NH * 32.0, [&] {
           return gemm_bf16_w4(EPI_QK_TATTN_LN, (const bf16_t*)xs, D, (const bf16_t*)lw.wqk, D, M, 2 * D, D, ep, s); }));
         vp::EpiArgs ev;
-        ev.ln_rs = ln_rs; ev.cap = cap; ev.heads = NH;
-        ev.out = hb; ev.ldo = D; ev.resid = big;
+        set_tattn_cap(ev, cap, NH);
+        ev.ln_rs = ln_rs; ev.out = hb; ev.ldo = D; ev.resid = big;
         ev.bias = lw.bqkv + 2 * D; ev.ln_c = lw.cqkv + 2 * D;
         const bf16_t* wv = static_cast<const bf16_t*>(lw.wqkv) + (size_t)2 * D * D;
         VP_HIP(rec(PC_GEMM_QKV_TATTN, 2.0 * dM * dD * dD, gbytes(dD, dD, dE, 0) + dM * NH * 32.0, [&] {
@@ -626,37 +630,8 @@ struct Fwd {
         VP_HIP(rec(PC_GEMM_QKV, 2.0 * dM * dD * 3 * dD, gbytes(dD, 3 * dD, dE, 0), [&] {
           return gemm(EPI_BF16, hb, D, lw.wqkv, 3 * D, big, 3 * D, lw.bqkv, nullptr, nullptr, 1, nullptr); }));
       }
-      // fp32 sequences longer than 256 (the auxiliary encoder, long clips' temporal attention, large patch grids): the
-      // MFMA kernel for 0 < cap <= 50, else the generic online-softmax one
-      auto attention_f32_long = [&](int ns, int len, const float* kpad) {
-        const hipError_t e = attention_f32_mfma((const float*)big, (float*)hb, ns, len, NH, cap, kpad, s);
-        return e != hipErrorNotSupported ? e : attention_masked(big, hb, 0, ns, len, NH, cap, kpad, 0, s);
-      };
       if (!tattn) VP_HIP(rec(acls, aflops, abytes, [&] {
-        if (kind == ATT_TEXT) {
-          if (bf && fast_cap(cap) && S > 16 && S <= 256)
-            return attention_seq_bf16((const bf16_t*)big, (bf16_t*)hb, num_seq, S, NH, cap, pad, s, causal);
-          return attention_masked(big, hb, bf, num_seq, S, NH, cap, pad, causal, s);
-        }
-        // the bf16 kernels' max-free softmax needs 0 < cap <= kMaxFastCap; cap <= 0 (no capping,
-        // layers.py:586-589) or a larger cap runs the online-softmax kernel
-        if (bf && !fast_cap(cap)) return attention_masked(big, hb, 1, num_seq, S, NH, cap, pad, 0, s);
-        if (kind == ATT_LONG) {  // no masks (encoders.py:855); any T*N
-          if (!bf) return attention_f32_long(num_seq, S, nullptr);
-          if (S >= 256) return attention_long_bf16((const bf16_t*)big, (bf16_t*)hb, num_seq, S, NH, cap, s);
-          if (S > 16) return attention_seq_bf16((const bf16_t*)big, (bf16_t*)hb, num_seq, S, NH, cap, nullptr, s);
-          return attention_temporal_bf16((const bf16_t*)big, (bf16_t*)hb, num_seq, S, NH, cap, nullptr, s);
-        }
-        // 16 < S <= 256 (T > 16 frames, other patch grids) on the sequence-packed MFMA kernel; longer sequences
-        // on the generic fp32-math kernel
-        if (!bf) {
-          if (S <= 256) return attention_f32((const float*)big, (float*)hb, num_seq, S, NH, cap, pad, s);
-          return attention_f32_long(num_seq, S, pad);
-        }
-        if (S == 256) return attention_spatial_bf16((const bf16_t*)big, (bf16_t*)hb, num_seq, NH, cap, pad, s, sblk);
-        if (S <= 16) return attention_temporal_bf16((const bf16_t*)big, (bf16_t*)hb, num_seq, S, NH, cap, pad, s);
-        if (S <= 256) return attention_seq_bf16((const bf16_t*)big, (bf16_t*)hb, num_seq, S, NH, cap, pad, s);
-        return attention_masked(big, hb, 1, num_seq, S, NH, cap, pad, 0, s); }));
+        return launch_attention(kind, bf, big, hb, num_seq, S, NH, cap, pad, causal, sblk, s); }));
       VP_HIP(rec(PC_GEMM_POST, 2.0 * dM * dD * dD, gbytes(dD, dD, dE, dE), [&] {
         return gemm(fold ? EPI_RESID_BF16_ST : epi_resid, hb, D, lw.wpost, D, xs, D, lw.bpost, xs, nullptr, 1,
                     nullptr); }));

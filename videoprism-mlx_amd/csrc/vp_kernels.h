@@ -143,7 +143,8 @@ hipError_t attention_temporal_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, in
 hipError_t attention_f32(const float* qkv, float* o, int num_seq, int S, int heads, float cap,
                          const float* key_pad, hipStream_t s);
 // fp32 on v_mfma_f32_32x32x2f32, any S, no causal mask: hipErrorNotSupported unless 0 < cap <= 50 (the
-// max-free softmax); the callers then take the generic online-softmax kernels
+// max-free softmax), which is when the host chooses it (vp_internal.h choose_attention); attention_f32 then
+// takes its generic kernel
 hipError_t attention_f32_mfma(const float* qkv, float* o, int num_seq, int S, int heads, float cap,
                               const float* key_pad, hipStream_t s);
 

@@ -148,6 +148,8 @@ _SIGNATURES = {
     "vp_dev_attention_spatial_blk": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_void_p, c_void_p]),
     "vp_dev_gemm_tattn": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    # which attention kernel the library picks (vpi::choose_attention); no GPU call
+    "vp_dev_attention_choice": (c_int, [c_int, c_int, c_int64, c_float, c_int]),
 }
 # diag library only (ablation builds for tools/)
 _DIAG_SIGNATURES = {
@@ -360,6 +362,20 @@ def dev_ln_stats(src, M, D, out, from_partials, stream=None):
     """(rstd, -mean*rstd) per row from partial statistics (from_partials) or bf16 rows."""
     call("vp_dev_ln_stats", 0 if from_partials else 1, _ptr(src), M, D, _ptr(out), _stream(stream))
     return out
+
+
+# vp_dev_attention_choice: stack kinds (vp_internal.h AttnKind; ATT_OP: as vp_op_attention maps S and the key
+# paddings) and the kernels it returns (AttnKernel)
+ATT_OP, ATT_VIDEO, ATT_LONG, ATT_TEXT = -1, 0, 1, 2
+ATTN_KERNELS = ("SPATIAL", "TEMPORAL", "SEQ", "LONG", "MASKED", "F32", "F32_MFMA")
+
+
+def dev_attention_choice(kind, precision, S, cap, has_key_pad=False) -> str:
+    """Name of the attention kernel a stack of `kind` gets (no GPU call, no device needed)."""
+    k = load().vp_dev_attention_choice(kind, precision, S, float(cap), 1 if has_key_pad else 0)
+    if k < 0:
+        raise ValueError(f"bad argument: kind {kind}, precision {precision}, S {S}")
+    return ATTN_KERNELS[k]
 
 
 def op_attention(qkv, num_seq, S, heads, cap, key_pad=None, out=None, stream=None):

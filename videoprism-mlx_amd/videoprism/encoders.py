@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes
 import dataclasses
+import weakref
 from collections.abc import Collection
 from typing import Any
 
@@ -43,138 +44,176 @@ def _check_device(t, device: int, what: str) -> None:
         raise ValueError(f"{what} must be on cuda:{device} (the engine's device), got {t.device}")
 
 
-def _profile_enable(handle, capacity: int) -> None:
-    _native.call("vp_profile_enable", handle, int(capacity))
-
-
-def _profile_set_mask(handle, names=None) -> None:
-    """Restrict events to the named kernel classes (None: all)."""
-    mask = 0xFFFFFFFF
-    if names is not None:
-        lib = _native.load()
-        mask = 0
-        for i in range(lib.vp_profile_class_count()):
-            name = ctypes.c_char_p()
-            _native.call("vp_profile_class_name", i, ctypes.byref(name))
-            if name.value.decode() in names:
-                mask |= 1 << i
-    _native.call("vp_profile_set_mask", handle, mask)
-
-
-def _profile_read(handle) -> dict:
-    """{kernel class: {ms, flops, bytes, launches}} since the previous read (vp_profile_read)."""
+def _profile_class_names() -> list:
     lib = _native.load()
-    n = lib.vp_profile_class_count()
-    ms = (ctypes.c_double * n)()
-    fl = (ctypes.c_double * n)()
-    by = (ctypes.c_double * n)()
-    la = (ctypes.c_int64 * n)()
-    _native.call("vp_profile_read", handle, n, ms, fl, by, la)
-    out = {}
-    for i in range(n):
+    names = []
+    for i in range(lib.vp_profile_class_count()):
         name = ctypes.c_char_p()
         _native.call("vp_profile_class_name", i, ctypes.byref(name))
-        if la[i]:
-            out[name.value.decode()] = dict(ms=ms[i], flops=fl[i], bytes=by[i], launches=la[i])
-    return out
+        names.append(name.value.decode())
+    return names
 
 
-def _prepare_shape(handle, seen: set, H: int, W: int, T: int) -> None:
-    """First sight of a frame size / clip length: the interpolated spatial (encoders.py:497-512)
-    and temporal (:543-553) positional tables, cached on the device by the library (the
-    forward itself never allocates)."""
-    if (H, W) not in seen:
-        _native.call("vp_prepare_geometry", handle, H, W)
-        seen.add((H, W))
-    if T not in seen:
-        _native.call("vp_prepare_frames", handle, T)
-        seen.add(T)
+def _vp_config(cfg: dict, bf16: bool):
+    return _native.vp_config(
+        patch_size=cfg["patch_size"], pos_emb_t=cfg["pos_emb_shape"][0],
+        pos_emb_h=cfg["pos_emb_shape"][1], pos_emb_w=cfg["pos_emb_shape"][2],
+        model_dim=cfg["model_dim"], num_spatial_layers=cfg["num_spatial_layers"],
+        num_temporal_layers=cfg["num_temporal_layers"], num_heads=cfg["num_heads"],
+        mlp_dim=cfg["mlp_dim"], atten_logit_cap=float(cfg.get("atten_logit_cap", 0.0)),
+        fprop_dtype=_native.VP_BF16 if bf16 else _native.VP_F32)
 
 
-class Engine:
-    """One vp_handle (packed weights on one device) plus a reusable workspace."""
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+class _EngineBase:
+    """One native handle (packed weights on one device) plus its grow-only workspaces.  A subclass
+    names its C entry points (`_PREFIX`_create / _set_param / _finalize / _destroy) and gives the
+    arguments of its create call ahead of (device, &handle)."""
+
+    _PREFIX = ""
 
     def __init__(self, cfg: dict, flat_params: dict, device: int, bf16: bool):
         self.cfg = dict(cfg)
         self.device = device
         self.bf16 = bf16
         lib = _native.load()
-        c = _native.vp_config(
-            patch_size=cfg["patch_size"], pos_emb_t=cfg["pos_emb_shape"][0],
-            pos_emb_h=cfg["pos_emb_shape"][1], pos_emb_w=cfg["pos_emb_shape"][2],
-            model_dim=cfg["model_dim"], num_spatial_layers=cfg["num_spatial_layers"],
-            num_temporal_layers=cfg["num_temporal_layers"], num_heads=cfg["num_heads"],
-            mlp_dim=cfg["mlp_dim"], atten_logit_cap=float(cfg.get("atten_logit_cap", 0.0)),
-            fprop_dtype=_native.VP_BF16 if bf16 else _native.VP_F32)
+        fn = lambda name: getattr(lib, f"{self._PREFIX}_{name}")  # noqa: E731
         h = ctypes.c_void_p()
-        _native.check(lib.vp_create(ctypes.byref(c), device, ctypes.byref(h)))
-        self._h = h
+        _native.check(fn("create")(*self._create_args(), device, ctypes.byref(h)))
         try:
             for name, arr in flat_params.items():
                 a = np.ascontiguousarray(arr, dtype=np.float32)
                 shape = (ctypes.c_int64 * a.ndim)(*a.shape)
-                _native.check(lib.vp_set_param(h, name.encode(), a.ctypes.data_as(ctypes.c_void_p),
-                                               shape, a.ndim))
-            _native.check(lib.vp_finalize(h))
+                _native.check(fn("set_param")(h, name.encode(), a.ctypes.data_as(ctypes.c_void_p),
+                                              shape, a.ndim))
+            _native.check(fn("finalize")(h))
         except Exception:
-            lib.vp_destroy(h)
-            self._h = None
+            fn("destroy")(h)
             raise
-        self._ws = None
+        self._h = h
+        # bound to the library's function and the handle value, not to this object or the module's
+        # globals: it still runs (once) when the interpreter is shutting down
+        weakref.finalize(self, fn("destroy"), h)
+        self._ws = {}
         self._grids = set()
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _native._lib is not None:
-            _native._lib.vp_destroy(h)
-            self._h = None
+    def _create_args(self) -> tuple:
+        raise NotImplementedError
+
+    def video_handle(self):
+        """The vp_handle of the encoder (its profiler and positional tables live there)."""
+        v = ctypes.c_void_p()
+        _native.call(f"{self._PREFIX}_video_handle", self._h, ctypes.byref(v))
+        return v
 
     # -- live per-kernel timing (HIP events on the launch stream, vp_profile_*) ---------
     def profile_enable(self, capacity: int) -> None:
-        _profile_enable(self._h, capacity)
-
-    def profile_read(self) -> dict:
-        return _profile_read(self._h)
+        """HIP events around every launch of the handle (for an LvT engine: both towers)."""
+        _native.call("vp_profile_enable", self.video_handle(), int(capacity))
 
     def profile_only(self, names=None) -> None:
-        _profile_set_mask(self._h, names)
+        """Restrict events to the named kernel classes (None: all)."""
+        mask = 0xFFFFFFFF
+        if names is not None:
+            mask = sum(1 << i for i, name in enumerate(_profile_class_names()) if name in names)
+        _native.call("vp_profile_set_mask", self.video_handle(), mask)
+
+    def profile_read(self) -> dict:
+        """{kernel class: {ms, flops, bytes, launches}} since the previous read (vp_profile_read)."""
+        names = _profile_class_names()
+        n = len(names)
+        ms = (ctypes.c_double * n)()
+        fl = (ctypes.c_double * n)()
+        by = (ctypes.c_double * n)()
+        la = (ctypes.c_int64 * n)()
+        _native.call("vp_profile_read", self.video_handle(), n, ms, fl, by, la)
+        return {names[i]: dict(ms=ms[i], flops=fl[i], bytes=by[i], launches=la[i])
+                for i in range(n) if la[i]}
 
     def kernel_name(self, cls_name: str) -> str:
         """Short symbol of the kernel behind profiler class `cls_name` (last launch)."""
-        return _native.profile_kernel_name(self._h, cls_name)
+        return _native.profile_kernel_name(self.video_handle(), cls_name)
 
-    def workspace(self, B, T, H, W):
-        torch = _torch()
+    def _workspace(self, key: str, query: str, *dims):
+        """The cached workspace `key`, regrown if `query`(handle, *dims, &bytes) asks for more."""
         n = ctypes.c_size_t()
-        _native.call("vp_workspace_bytes", self._h, B, T, H, W, ctypes.byref(n))
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = None
-            self._ws = torch.empty(max(n.value, 256), dtype=torch.uint8,
-                                   device=f"cuda:{self.device}")
-        return self._ws
+        _native.call(query, self._h, *dims, ctypes.byref(n))
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < n.value:
+            ws = self._ws[key] = None  # the old one is freed before the new one is allocated
+            ws = _torch().empty(max(n.value, 256), dtype=_torch().uint8, device=f"cuda:{self.device}")
+            self._ws[key] = ws
+        return ws
 
-    def forward(self, video, frame_paddings=None, out_dtype=None, want_spatial=False,
-                out=None, stream=None):
-        """video: CUDA tensor [B,T,H,W,3] (fp32 or bf16) on this engine's device."""
+    def _stream(self, stream):
+        s = stream if stream is not None else _torch().cuda.current_stream(self.device)
+        return ctypes.c_void_p(s.cuda_stream)
+
+    def _check_video(self, video, frame_paddings):
+        """-> (video as the C-ABI takes it, its dtype code, frame paddings [B, T] fp32 or None, B, T, H, W,
+        tokens per frame), with the positional tables for this frame size and clip length prepared."""
         torch = _torch()
         if video.dim() != 5:
             raise ValueError(f"inputs must be [B, T, H, W, 3], got {tuple(video.shape)}")
         B, T, H, W, C = video.shape
         if C != 3:
             raise ValueError("inputs must have 3 channels")
-        _check_device(video, self.device, "video")
-        video = video.contiguous()
-        if video.dtype not in (torch.bfloat16, torch.float32, torch.uint8):
-            video = video.float()
-        in_dt = _native._prec(video)  # uint8 frames are normalised /255 on device
-        out_dtype = out_dtype or (torch.bfloat16 if self.bf16 else torch.float32)
         P = self.cfg["patch_size"]
         if H % P or W % P:
             raise ValueError(f"Image height ({H}) and width ({W}) should be multiples "
                              f"of patch_size ({P}).")
-        N = (H // P) * (W // P)
+        _check_device(video, self.device, "video")
+        video = video.contiguous()
+        if video.dtype not in (torch.bfloat16, torch.float32, torch.uint8):
+            video = video.float()
+        fp = None
+        if frame_paddings is not None:
+            fp = frame_paddings.to(device=video.device, dtype=torch.float32).contiguous()
+            if tuple(fp.shape) != (B, T):
+                raise AssertionError(f"frame_paddings.shape == {(B, T)} failed (encoders.py:442)")
+        # first sight of a frame size / clip length: the interpolated spatial (encoders.py:497-512) and
+        # temporal (:543-553) positional tables, cached on the device by the library (the forward
+        # itself never allocates)
+        if (H, W) not in self._grids:
+            _native.call("vp_prepare_geometry", self.video_handle(), H, W)
+            self._grids.add((H, W))
+        if T not in self._grids:
+            _native.call("vp_prepare_frames", self.video_handle(), T)
+            self._grids.add(T)
+        # uint8 frames are normalised /255 on device
+        return video, _native._prec(video), fp, B, T, H, W, (H // P) * (W // P)
+
+    def _features(self, want: bool, B: int, L: int, device):
+        """A [B, L, D] buffer in the fprop dtype for spatial / spatio-temporal features, if wanted."""
+        torch = _torch()
+        return torch.empty((B, L, self.cfg["model_dim"]), dtype=torch.bfloat16 if self.bf16 else torch.float32,
+                           device=device) if want else None
+
+
+class Engine(_EngineBase):
+    """One vp_handle (packed weights on one device) plus a reusable workspace."""
+
+    _PREFIX = "vp"
+
+    def _create_args(self):
+        return (ctypes.byref(_vp_config(self.cfg, self.bf16)),)
+
+    def video_handle(self):
+        return self._h
+
+    def workspace(self, B, T, H, W):
+        return self._workspace("video", "vp_workspace_bytes", B, T, H, W)
+
+    def forward(self, video, frame_paddings=None, out_dtype=None, want_spatial=False,
+                out=None, stream=None):
+        """video: CUDA tensor [B,T,H,W,3] (fp32, bf16 or uint8) on this engine's device."""
+        torch = _torch()
+        video, in_dt, fp, B, T, H, W, N = self._check_video(video, frame_paddings)
+        out_dtype = out_dtype or (torch.bfloat16 if self.bf16 else torch.float32)
         D = self.cfg["model_dim"]
-        _prepare_shape(self._h, self._grids, H, W, T)
         if out is None:
             out = torch.empty((B, T * N, D), dtype=out_dtype, device=video.device)
         else:  # the kernels write B*T*N*D elements through the raw pointer
@@ -184,22 +223,29 @@ class Engine:
                 raise ValueError(f"out must be a contiguous bf16/fp32 tensor of shape {(B, T * N, D)}, "
                                  f"got {tuple(out.shape)} {out.dtype} contiguous={out.is_contiguous()}")
         sp = torch.empty_like(out) if want_spatial else None
-        fp = None
-        if frame_paddings is not None:
-            fp = frame_paddings.to(device=video.device, dtype=torch.float32).contiguous()
-            if tuple(fp.shape) != (B, T):
-                raise AssertionError(f"frame_paddings.shape == {(B, T)} failed (encoders.py:442)")
         if B == 0:  # an empty batch: the reference's zero-size result, nothing to launch
             return out, sp
         ws = self.workspace(B, T, H, W)
-        s = stream if stream is not None else torch.cuda.current_stream(video.device)
-        _native.call("vp_forward", self._h, ctypes.c_void_p(video.data_ptr()), in_dt, B, T, H, W,
-                     None if fp is None else ctypes.c_void_p(fp.data_ptr()),
-                     ctypes.c_void_p(out.data_ptr()),
-                     _native.VP_BF16 if out.dtype == torch.bfloat16 else _native.VP_F32,
-                     None if sp is None else ctypes.c_void_p(sp.data_ptr()),
-                     ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(s.cuda_stream))
+        _native.call("vp_forward", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp), _ptr(out),
+                     _native._prec(out), _ptr(sp), _ptr(ws), ws.numel(), self._stream(stream))
         return out, sp
+
+
+def _cached_engine(model, variables, device: int, norm_policy: str, make):
+    """The engine of `model` (one of the dataclasses below) for this parameter tree, device and
+    dtype: built by make(flat leaves) on first use, kept in model._engines while the tree lives."""
+    p = variables["params"] if isinstance(variables, dict) and "params" in variables else variables
+    key = (id(p), device, model.is_bf16)
+    ent = model._engines.get(key)
+    if ent is not None and ent[0] is p:
+        return ent[1]
+    if norm_policy != "pre":
+        raise NotImplementedError("only norm_policy='pre' is implemented (all public configs)")
+    flat = params_lib.canonical_params(variables)
+    params_lib.validate(flat, model.param_specs())
+    eng = make(flat)
+    model._engines[key] = (p, eng)
+    return eng
 
 
 @dataclasses.dataclass
@@ -244,18 +290,8 @@ class FactorizedEncoder:
         return params_lib.flax_default_init(self.config(), seed)
 
     def engine(self, variables, device: int) -> Engine:
-        p = variables["params"] if isinstance(variables, dict) and "params" in variables else variables
-        key = (id(p), device, self.is_bf16)
-        ent = self._engines.get(key)
-        if ent is not None and ent[0] is p:
-            return ent[1]
-        if self.norm_policy != "pre":
-            raise NotImplementedError("only norm_policy='pre' is implemented (all public configs)")
-        flat = params_lib.canonical_params(variables)
-        params_lib.validate(flat, self.param_specs())
-        eng = Engine(self.config(), flat, device, self.is_bf16)
-        self._engines[key] = (p, eng)
-        return eng
+        return _cached_engine(self, variables, device, self.norm_policy,
+                              lambda flat: Engine(self.config(), flat, device, self.is_bf16))
 
     def apply(self, variables, inputs, train: bool = False,
               return_intermediate: bool | Collection[str] = False, frame_paddings=None,
@@ -303,116 +339,37 @@ class FactorizedEncoder:
     __call__ = apply
 
 
-class ClipEngine:
+class ClipEngine(_EngineBase):
     """One vp_clip handle (packed LvT weights on one device) plus reusable workspaces."""
 
-    def __init__(self, cfg: dict, flat_params: dict, device: int, bf16: bool):
-        self.cfg = dict(cfg)
-        self.device = device
-        self.bf16 = bf16
-        lib = _native.load()
-        v = _native.vp_config(
-            patch_size=cfg["patch_size"], pos_emb_t=cfg["pos_emb_shape"][0],
-            pos_emb_h=cfg["pos_emb_shape"][1], pos_emb_w=cfg["pos_emb_shape"][2],
-            model_dim=cfg["model_dim"], num_spatial_layers=cfg["num_spatial_layers"],
-            num_temporal_layers=cfg["num_temporal_layers"], num_heads=cfg["num_heads"],
-            mlp_dim=cfg["mlp_dim"], atten_logit_cap=float(cfg.get("atten_logit_cap", 0.0)),
-            fprop_dtype=_native.VP_BF16 if bf16 else _native.VP_F32)
+    _PREFIX = "vp_clip"
+
+    def _create_args(self):
+        cfg = self.cfg
         c = _native.vp_clip_config(
-            video=v, num_auxiliary_layers=cfg.get("num_auxiliary_layers", 0),
+            video=_vp_config(cfg, self.bf16), num_auxiliary_layers=cfg.get("num_auxiliary_layers", 0),
             vocabulary_size=cfg["vocabulary_size"],
             num_unimodal_layers=cfg["num_unimodal_layers"],
             enable_causal_atten=1 if cfg.get("enable_causal_atten", True) else 0)
-        h = ctypes.c_void_p()
-        _native.check(lib.vp_clip_create(ctypes.byref(c), device, ctypes.byref(h)))
-        self._h = h
-        try:
-            for name, arr in flat_params.items():
-                a = np.ascontiguousarray(arr, dtype=np.float32)
-                shape = (ctypes.c_int64 * a.ndim)(*a.shape)
-                _native.check(lib.vp_clip_set_param(h, name.encode(),
-                                                    a.ctypes.data_as(ctypes.c_void_p), shape, a.ndim))
-            _native.check(lib.vp_clip_finalize(h))
-        except Exception:
-            lib.vp_clip_destroy(h)
-            self._h = None
-            raise
-        self._ws = {}
-        self._grids = set()
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _native._lib is not None:
-            _native._lib.vp_clip_destroy(h)
-            self._h = None
-
-    def video_handle(self):
-        v = ctypes.c_void_p()
-        _native.call("vp_clip_video_handle", self._h, ctypes.byref(v))
-        return v
-
-    def profile_enable(self, capacity: int) -> None:
-        """HIP events around every launch of both towers (vision, auxiliary, pooler, text)."""
-        _profile_enable(self.video_handle(), capacity)
-
-    def profile_read(self) -> dict:
-        return _profile_read(self.video_handle())
-
-    def profile_only(self, names=None) -> None:
-        _profile_set_mask(self.video_handle(), names)
-
-    def kernel_name(self, cls_name: str) -> str:
-        return _native.profile_kernel_name(self.video_handle(), cls_name)
-
-    def _workspace(self, key, nbytes):
-        torch = _torch()
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            self._ws[key] = None
-            ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=f"cuda:{self.device}")
-            self._ws[key] = ws
-        return ws
+        return (ctypes.byref(c),)
 
     def encode_video(self, video, frame_paddings=None, normalize=True, want_frames=False,
                      want_spatial=False, want_spatiotemporal=False, stream=None):
         torch = _torch()
-        B, T, H, W, C = video.shape
-        if C != 3:
-            raise ValueError("inputs must have 3 channels")
-        P = self.cfg["patch_size"]
-        if H % P or W % P:
-            raise ValueError(f"Image height ({H}) and width ({W}) should be multiples "
-                             f"of patch_size ({P}).")
-        _check_device(video, self.device, "video")
-        video = video.contiguous()
-        if video.dtype not in (torch.bfloat16, torch.float32, torch.uint8):
-            video = video.float()
-        in_dt = _native._prec(video)  # uint8 frames are normalised /255 on device
+        video, in_dt, fp, B, T, H, W, N = self._check_video(video, frame_paddings)
         D = self.cfg["model_dim"]
-        N = (H // P) * (W // P)
-        _prepare_shape(self.video_handle(), self._grids, H, W, T)
-        fdt = torch.bfloat16 if self.bf16 else torch.float32
         dev = video.device
         vemb = torch.empty((B, D), dtype=torch.float32, device=dev)
         femb = torch.empty((B, T, D), dtype=torch.float32, device=dev) if want_frames else None
-        sp = torch.empty((B, T * N, D), dtype=fdt, device=dev) if want_spatial else None
-        st = torch.empty((B, T * N, D), dtype=fdt, device=dev) if want_spatiotemporal else None
-        fp = None
-        if frame_paddings is not None:
-            fp = frame_paddings.to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(fp.shape) != (B, T):
-                raise AssertionError(f"frame_paddings.shape == {(B, T)} failed (encoders.py:442)")
+        sp = self._features(want_spatial, B, T * N, dev)
+        st = self._features(want_spatiotemporal, B, T * N, dev)
         if B == 0:  # an empty batch: zero-size embeddings, nothing to launch
             return vemb, femb, sp, st
-        n = ctypes.c_size_t()
-        _native.call("vp_clip_video_workspace_bytes", self._h, B, T, H, W, ctypes.byref(n))
-        ws = self._workspace("video", n.value)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        _native.call("vp_clip_encode_video", self._h, ptr(video), in_dt, B, T, H, W, ptr(fp),
-                     1 if normalize else 0, ptr(vemb), ptr(femb), ptr(sp), ptr(st),
-                     _native.VP_BF16 if self.bf16 else _native.VP_F32, ptr(ws), ws.numel(),
-                     ctypes.c_void_p(s.cuda_stream))
+        ws = self._workspace("video", "vp_clip_video_workspace_bytes", B, T, H, W)
+        _native.call("vp_clip_encode_video", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp),
+                     1 if normalize else 0, _ptr(vemb), _ptr(femb), _ptr(sp), _ptr(st),
+                     _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
+                     self._stream(stream))
         return vemb, femb, sp, st
 
     def encode_text(self, ids, paddings, normalize=True, stream=None):
@@ -423,18 +380,12 @@ class ClipEngine:
         pad = paddings.to(device=ids.device, dtype=torch.float32).contiguous()
         if tuple(pad.shape) != (Q, L):
             raise ValueError(f"text_paddings must be [{Q}, {L}], got {tuple(pad.shape)}")
-        D = self.cfg["model_dim"]
-        out = torch.empty((Q, D), dtype=torch.float32, device=ids.device)
+        out = torch.empty((Q, self.cfg["model_dim"]), dtype=torch.float32, device=ids.device)
         if Q == 0 and L >= 1:  # no queries: a zero-size result, nothing to launch
             return out
-        n = ctypes.c_size_t()
-        _native.call("vp_clip_text_workspace_bytes", self._h, Q, L, ctypes.byref(n))
-        ws = self._workspace("text", n.value)
-        s = stream if stream is not None else torch.cuda.current_stream(ids.device)
-        _native.call("vp_clip_encode_text", self._h, ctypes.c_void_p(ids.data_ptr()),
-                     ctypes.c_void_p(pad.data_ptr()), Q, L, 1 if normalize else 0,
-                     ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                     ctypes.c_void_p(s.cuda_stream))
+        ws = self._workspace("text", "vp_clip_text_workspace_bytes", Q, L)
+        _native.call("vp_clip_encode_text", self._h, _ptr(ids), _ptr(pad), Q, L, 1 if normalize else 0,
+                     _ptr(out), _ptr(ws), ws.numel(), self._stream(stream))
         return out
 
 
@@ -486,18 +437,8 @@ class FactorizedVideoCLIP:
         return params_lib.synthetic_params(self.config(), seed, specs=self.param_specs())
 
     def engine(self, variables, device: int) -> ClipEngine:
-        p = variables["params"] if isinstance(variables, dict) and "params" in variables else variables
-        key = (id(p), device, self.is_bf16)
-        ent = self._engines.get(key)
-        if ent is not None and ent[0] is p:
-            return ent[1]
-        if self.norm_policy != "pre":
-            raise NotImplementedError("only norm_policy='pre' is implemented (public LvT configs)")
-        flat = params_lib.canonical_params(variables)
-        params_lib.validate(flat, self.param_specs())
-        eng = ClipEngine(self.config(), flat, device, self.is_bf16)
-        self._engines[key] = (p, eng)
-        return eng
+        return _cached_engine(self, variables, device, self.norm_policy,
+                              lambda flat: ClipEngine(self.config(), flat, device, self.is_bf16))
 
     def apply(self, variables, inputs=None, text_token_ids=None, text_paddings=None,
               train: bool = False, normalize: bool = True,
@@ -562,92 +503,35 @@ class FactorizedVideoCLIP:
     __call__ = apply
 
 
-class ClassifierEngine:
+class ClassifierEngine(_EngineBase):
     """One vp_classifier handle (FactorizedVideoClassifier weights on one device)."""
 
+    _PREFIX = "vp_classifier"
+
     def __init__(self, cfg: dict, num_classes: int, flat_params: dict, device: int, bf16: bool):
-        self.cfg = dict(cfg)
         self.num_classes = num_classes
-        self.device = device
-        self.bf16 = bf16
-        lib = _native.load()
-        v = _native.vp_config(
-            patch_size=cfg["patch_size"], pos_emb_t=cfg["pos_emb_shape"][0],
-            pos_emb_h=cfg["pos_emb_shape"][1], pos_emb_w=cfg["pos_emb_shape"][2],
-            model_dim=cfg["model_dim"], num_spatial_layers=cfg["num_spatial_layers"],
-            num_temporal_layers=cfg["num_temporal_layers"], num_heads=cfg["num_heads"],
-            mlp_dim=cfg["mlp_dim"], atten_logit_cap=float(cfg.get("atten_logit_cap", 0.0)),
-            fprop_dtype=_native.VP_BF16 if bf16 else _native.VP_F32)
-        h = ctypes.c_void_p()
-        _native.check(lib.vp_classifier_create(ctypes.byref(v), num_classes, device, ctypes.byref(h)))
-        self._h = h
-        try:
-            for name, arr in flat_params.items():
-                a = np.ascontiguousarray(arr, dtype=np.float32)
-                shape = (ctypes.c_int64 * a.ndim)(*a.shape)
-                _native.check(lib.vp_classifier_set_param(h, name.encode(),
-                                                          a.ctypes.data_as(ctypes.c_void_p), shape,
-                                                          a.ndim))
-            _native.check(lib.vp_classifier_finalize(h))
-        except Exception:
-            lib.vp_classifier_destroy(h)
-            self._h = None
-            raise
-        self._ws = None
-        self._grids = set()
+        super().__init__(cfg, flat_params, device, bf16)
 
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and _native._lib is not None:
-            _native._lib.vp_classifier_destroy(h)
-            self._h = None
-
-    def video_handle(self):
-        v = ctypes.c_void_p()
-        _native.call("vp_classifier_video_handle", self._h, ctypes.byref(v))
-        return v
+    def _create_args(self):
+        return (ctypes.byref(_vp_config(self.cfg, self.bf16)), self.num_classes)
 
     def forward(self, video, frame_paddings=None, want_embeddings=False, want_spatial=False,
                 want_spatiotemporal=False, stream=None):
         torch = _torch()
-        B, T, H, W, C = video.shape
-        P = self.cfg["patch_size"]
-        if C != 3:
-            raise ValueError("inputs must have 3 channels")
-        if H % P or W % P:
-            raise ValueError(f"Image height ({H}) and width ({W}) should be multiples "
-                             f"of patch_size ({P}).")
-        _check_device(video, self.device, "video")
-        video = video.contiguous()
-        if video.dtype not in (torch.bfloat16, torch.float32, torch.uint8):
-            video = video.float()
-        in_dt = _native._prec(video)
-        _prepare_shape(self.video_handle(), self._grids, H, W, T)
-        D, N = self.cfg["model_dim"], (H // P) * (W // P)
+        video, in_dt, fp, B, T, H, W, N = self._check_video(video, frame_paddings)
+        D = self.cfg["model_dim"]
         dev = video.device
-        fdt = torch.bfloat16 if self.bf16 else torch.float32
         logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
         emb = torch.empty((B, D), dtype=torch.float32, device=dev) if want_embeddings else None
-        sp = torch.empty((B, T * N, D), dtype=fdt, device=dev) if want_spatial else None
-        st = torch.empty((B, T * N, D), dtype=fdt, device=dev) if want_spatiotemporal else None
-        fp = None
-        if frame_paddings is not None:
-            fp = frame_paddings.to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(fp.shape) != (B, T):
-                raise AssertionError(f"frame_paddings.shape == {(B, T)} failed (encoders.py:442)")
+        sp = self._features(want_spatial, B, T * N, dev)
+        st = self._features(want_spatiotemporal, B, T * N, dev)
         if B == 0:  # an empty batch: zero-size logits, nothing to launch
             return logits, emb, sp, st
-        n = ctypes.c_size_t()
-        _native.call("vp_classifier_workspace_bytes", self._h, B, T, H, W, ctypes.byref(n))
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = None
-            self._ws = torch.empty(max(n.value, 256), dtype=torch.uint8, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream(dev)
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        _native.call("vp_classifier_forward", self._h, ptr(video), in_dt, B, T, H, W, ptr(fp),
-                     ptr(logits), ptr(emb), ptr(sp), ptr(st),
-                     _native.VP_BF16 if self.bf16 else _native.VP_F32, ptr(self._ws),
-                     self._ws.numel(), ctypes.c_void_p(s.cuda_stream))
+        ws = self._workspace("video", "vp_classifier_workspace_bytes", B, T, H, W)
+        _native.call("vp_classifier_forward", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp),
+                     _ptr(logits), _ptr(emb), _ptr(sp), _ptr(st),
+                     _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
+                     self._stream(stream))
         return logits, emb, sp, st
 
 
@@ -681,18 +565,9 @@ class FactorizedVideoClassifier:
         return params_lib.synthetic_params(self.config(), seed, specs=self.param_specs())
 
     def engine(self, variables, device: int) -> ClassifierEngine:
-        p = variables["params"] if isinstance(variables, dict) and "params" in variables else variables
-        key = (id(p), device, self.is_bf16)
-        ent = self._engines.get(key)
-        if ent is not None and ent[0] is p:
-            return ent[1]
-        if self.encoder_params.get("norm_policy", "pre") != "pre":
-            raise NotImplementedError("only norm_policy='pre' is implemented")
-        flat = params_lib.canonical_params(variables)
-        params_lib.validate(flat, self.param_specs())
-        eng = ClassifierEngine(self.config(), self.num_classes, flat, device, self.is_bf16)
-        self._engines[key] = (p, eng)
-        return eng
+        return _cached_engine(
+            self, variables, device, self.encoder_params.get("norm_policy", "pre"),
+            lambda flat: ClassifierEngine(self.config(), self.num_classes, flat, device, self.is_bf16))
 
     def apply(self, variables, inputs, train: bool = False,
               return_intermediate: bool | Collection[str] = False, frame_paddings=None, **kwargs):
