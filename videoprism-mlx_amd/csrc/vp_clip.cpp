@@ -192,6 +192,22 @@ void build_clip_expected(vp_clip& c) {
   c.expect("text_encoder/unimodal_ln/bias", {D});
 }
 
+// bf16 hi/lo split of U [H][D] for the MFMA logits kernel: ut [32][D] = (U_hi | U_lo | 0), U_hi the bf16 of
+// U and U_lo the bf16 of U - U_hi (pack_pooler, and vp_dev_pool_split_u for the tests)
+void pool_split_u(const float* U, int64_t H, int64_t D, uint16_t* ut) {
+  std::fill(ut, ut + (size_t)32 * D, (uint16_t)0);
+  for (int64_t h = 0; h < H; ++h)
+    for (int64_t d = 0; d < D; ++d) {
+      const float u = U[(size_t)h * D + d];
+      const uint16_t hi = host_f2bf(u);
+      uint32_t hb = (uint32_t)hi << 16;
+      float hf;
+      std::memcpy(&hf, &hb, 4);
+      ut[(size_t)h * D + d] = hi;
+      ut[(size_t)(H + h) * D + d] = host_f2bf(u - hf);
+    }
+}
+
 // AttenTokenPoolingLayer (layers.py:1044-1136) with the query folded into the key projection
 // (see clip_kernels.hip): host packing in fp64.
 int pack_pooler(ParamStore& c, const std::string& root, int64_t D, int64_t H, int64_t dp, PoolerW& pw) {
@@ -230,18 +246,8 @@ int pack_pooler(ParamStore& c, const std::string& root, int64_t D, int64_t H, in
   std::vector<float> g(D);
   const auto& sc = c.data(root + "pooling_attention_layer_norm/scale");
   for (int64_t d = 0; d < D; ++d) g[d] = sc[d] + 1.0f;
-  // bf16 hi/lo split of U for the MFMA logits kernel
-  std::vector<uint16_t> ut((size_t)32 * D, 0);
-  for (int64_t h = 0; h < H; ++h)
-    for (int64_t d = 0; d < D; ++d) {
-      const float u = U[(size_t)h * D + d];
-      const uint16_t hi = host_f2bf(u);
-      uint32_t hb = (uint32_t)hi << 16;
-      float hf;
-      std::memcpy(&hf, &hb, 4);
-      ut[(size_t)h * D + d] = hi;
-      ut[(size_t)(H + h) * D + d] = host_f2bf(u - hf);
-    }
+  std::vector<uint16_t> ut((size_t)32 * D);
+  pool_split_u(U.data(), H, D, ut.data());
   int rc;
   if ((rc = c.upload(ut.data(), ut.size() * 2, &pw.Ut))) return rc;
   if ((rc = c.upload_f32(U, &pw.U)) || (rc = c.upload_f32(wvt, &pw.WvT)) || (rc = c.upload_f32(bv, &pw.bv)) ||
@@ -640,6 +646,159 @@ int vp_classifier_forward(vp_classifier* c, const void* video, int in_dtype, int
                             advance(spatial_out, b0 * st_clip), advance(spatiotemporal_out, b0 * st_clip), workspace,
                             stream);
   });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Not in the public header: the pooler, small GEMM and text kernels of clip_kernels.hip one at a time, and
+// run_pooler on caller-supplied tokens, for the op-level fp64 parity tests (tests/test_gpu_clip_kernels.py,
+// tests/test_pool_split_cpu.py).  Every shape a launcher would refuse is refused here first, with a message.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+bool float_dtype(int dtype) { return dtype == VP_F32 || dtype == VP_BF16; }
+
+// scratch of one run_pooler call over G groups of S rows: PoolScratch's fields in order, zpart holding the
+// G * pool_chunks(S) chunk sums (as pool_video_ws sizes it for its larger grouping)
+struct DevPoolWs {
+  size_t logits = 0, stats = 0, zpart = 0, z = 0, enc = 0, pooled = 0, total = 0;
+};
+
+DevPoolWs dev_pool_ws(int64_t G, int64_t S, int64_t D, int64_t NH, int64_t dp) {
+  DevPoolWs L;
+  size_t off = 0;
+  L.logits = off; off = align256(off + (size_t)G * S * NH * 4);
+  L.stats = off; off = align256(off + (size_t)G * NH * 8);
+  L.zpart = off; off = align256(off + (size_t)G * vp::pool_chunks((int)S) * NH * D * 4);
+  L.z = off; off = align256(off + (size_t)G * NH * D * 4);
+  L.enc = off; off = align256(off + (size_t)G * NH * dp * 4);
+  L.pooled = off; off = align256(off + (size_t)G * D * 4);
+  L.total = off;
+  return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Host only, no GPU call: the production packing of U [H][D] fp32 into ut [32][D] bf16 bits (pool_split_u).
+int vp_dev_pool_split_u(const float* U_host, int64_t H, int64_t D, uint16_t* ut_host) {
+  if (!U_host || !ut_host) return fail(VP_EINVAL, "null argument");
+  if (H < 1 || H > 16 || D < 1) return fail(VP_EINVAL, "pool_split_u: 1 <= H <= 16 and D >= 1");
+  pool_split_u(U_host, H, D, ut_host);
+  return VP_OK;
+}
+
+int vp_dev_pool_chunks(int64_t S) { return S < 1 || S > 0x7fffffff ? -1 : vp::pool_chunks((int)S); }
+
+// logits [rows/S][H][S] = x [rows][D] . U [H][D]; Ut: the split of vp_dev_pool_split_u on the device, or NULL
+int vp_dev_pool_logits(const void* x, int in_dtype, int64_t rows, int64_t S, int64_t D, const float* U,
+                       const void* Ut, int64_t H, float* logits, void* stream) {
+  if (!x || !U || !logits) return fail(VP_EINVAL, "null argument");
+  if (!float_dtype(in_dtype)) return fail(VP_EINVAL, "bad dtype");
+  if (rows < 1 || S < 1 || rows % S) return fail(VP_EINVAL, "pool_logits: rows must be a positive multiple of S");
+  if (D < 64 || D % 64 || D > 1024) return fail(VP_EINVAL, "pool_logits: D must be a multiple of 64, at most 1024");
+  if (H < 1 || H > 16) return fail(VP_EINVAL, "pool_logits: 1 <= H <= 16");
+  if (rows / 64 + 1 > 0x7fffffff) return fail(VP_EINVAL, "pool_logits: too many rows");
+  VP_HIP(vp::pool_logits(x, in_dtype == VP_BF16, rows, (int)S, (int)D, U, (const vp::bf16_t*)Ut, (int)H, logits,
+                         static_cast<hipStream_t>(stream)));
+  return VP_OK;
+}
+
+// stats [G*H][2] = (max, 1/sum exp(l - max)), z [G][H][D] = sum_s softmax(logits)[g][h][s] x[g*S+s];
+// zpart: scratch of [G][vp_dev_pool_chunks(S)][H][D] floats
+int vp_dev_pool_softmax_wsum(const void* x, int in_dtype, int64_t G, int64_t S, int64_t D, int64_t H,
+                             const float* logits, float* stats, float* zpart, float* z, void* stream) {
+  if (!x || !logits || !stats || !zpart || !z) return fail(VP_EINVAL, "null argument");
+  if (!float_dtype(in_dtype)) return fail(VP_EINVAL, "bad dtype");
+  if (G < 1 || S < 1 || G * S > 0x7fffffff) return fail(VP_EINVAL, "pool_softmax_wsum: bad G or S");
+  if (D < 256 || D % 256 || D > 1024)
+    return fail(VP_EINVAL, "pool_softmax_wsum: D must be a multiple of 256, at most 1024");
+  if (H < 1 || H > 16) return fail(VP_EINVAL, "pool_softmax_wsum: 1 <= H <= 16");
+  VP_HIP(vp::pool_softmax_wsum(x, in_dtype == VP_BF16, (int)G, (int)S, (int)D, (int)H, logits, stats, zpart, z,
+                               static_cast<hipStream_t>(stream)));
+  return VP_OK;
+}
+
+// splits == 0: small_gemm (batch matrices at strides sA / sW / sB / sO); splits >= 1: small_gemm_splitk
+// (batch == 1, part [splits][M][N] floats of scratch)
+int vp_dev_small_gemm(const float* A, int64_t lda, int64_t sA, const float* Wt, int64_t sW, const float* bias,
+                      int64_t sB, float* out, int64_t ldo, int64_t sO, int64_t M, int64_t N, int64_t K,
+                      int64_t batch, int64_t splits, float* part, void* stream) {
+  if (!A || !Wt || !out) return fail(VP_EINVAL, "null argument");
+  if (M < 1 || N < 1 || K < 1 || batch < 1) return fail(VP_EINVAL, "small_gemm: M, N, K and batch must be positive");
+  if ((M + 31) / 32 > 65535 || batch > 65535 || N > 0x7fffffff || K > 0x7fffffff)
+    return fail(VP_EINVAL, "small_gemm: shape out of range");
+  if (lda < K || ldo < N) return fail(VP_EINVAL, "small_gemm: lda >= K and ldo >= N");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (splits == 0) {
+    VP_HIP(vp::small_gemm(A, lda, sA, Wt, sW, bias, sB, out, ldo, sO, (int)M, (int)N, (int)K, (int)batch, s));
+    return VP_OK;
+  }
+  if (splits < 0 || splits > 65535) return fail(VP_EINVAL, "small_gemm: bad splits");
+  if (batch != 1 || !part) return fail(VP_EINVAL, "small_gemm: split-K needs batch == 1 and the partials buffer");
+  if (K % splits) return fail(VP_EINVAL, "small_gemm: K must be a multiple of splits");
+  VP_HIP(vp::small_gemm_splitk(A, lda, Wt, bias, out, ldo, (int)M, (int)N, (int)K, (int)splits, part, s));
+  return VP_OK;
+}
+
+// out [rows][D] fp32 = LayerNorm (gamma = 1 + scale, beta; skipped when gamma is NULL) then L2 (if do_l2) of
+// the rows x + r * stride
+int vp_dev_ln_l2_rows(const void* x, int in_dtype, int64_t stride, int64_t rows, int64_t D, const float* gamma,
+                      const float* beta, int do_l2, float* out, void* stream) {
+  if (!x || !out || (gamma && !beta)) return fail(VP_EINVAL, "null argument");
+  if (!float_dtype(in_dtype)) return fail(VP_EINVAL, "bad dtype");
+  if (D < 1 || D > 1024) return fail(VP_EINVAL, "ln_l2_rows: 1 <= D <= 1024");
+  if (rows < 1 || rows > 0x7fffffff || stride < D) return fail(VP_EINVAL, "ln_l2_rows: rows >= 1 and stride >= D");
+  VP_HIP(vp::ln_l2_rows(x, in_dtype == VP_BF16, stride, (int)rows, (int)D, gamma, beta, do_l2, out,
+                        static_cast<hipStream_t>(stream)));
+  return VP_OK;
+}
+
+// out [Q][L+1][D] = table[clamp(ids)] * scale + pos[t] for t < L, cls * scale at t = L; pad_out [Q][L+1] =
+// [pad_in | 0].  ids, pad_in and pos are not read when L == 0.
+int vp_dev_text_embed(const int32_t* ids, int64_t Q, int64_t L, const void* table, int table_dtype, int64_t V,
+                      const float* cls, const float* pos, float scale, int64_t D, void* out, int out_dtype,
+                      const float* pad_in, float* pad_out, void* stream) {
+  if (!table || !cls || !out || !pad_out || (L > 0 && (!ids || !pos || !pad_in))) return fail(VP_EINVAL, "null argument");
+  if (!float_dtype(table_dtype) || !float_dtype(out_dtype)) return fail(VP_EINVAL, "bad dtype");
+  if (Q < 1 || L < 0 || V < 1 || D < 1 || V > 0x7fffffff || D > 0x7fffffff || Q * (L + 1) > 0x7fffffff)
+    return fail(VP_EINVAL, "text_embed: Q >= 1, L >= 0, V >= 1, D >= 1");
+  VP_HIP(vp::text_embed(ids, (int)Q, (int)L, table, table_dtype == VP_BF16, (int)V, cls, pos, scale, (int)D, out,
+                        out_dtype == VP_BF16, pad_in, pad_out, static_cast<hipStream_t>(stream)));
+  return VP_OK;
+}
+
+// run_pooler with the packed weights of a finalized vp_clip (kind 0) or vp_classifier (kind 1) over caller
+// tokens feat [G*S][D] in the handle's fprop dtype -> dst [G][D] fp32.  scratch == NULL: only writes the
+// bytes it needs to *scratch_bytes.
+int vp_dev_pooler(int kind, void* handle, const void* feat, int64_t G, int64_t S, int do_l2, float* dst,
+                  void* scratch, size_t* scratch_bytes, void* stream) {
+  if (!handle || !scratch_bytes) return fail(VP_EINVAL, "null argument");
+  if (kind != 0 && kind != 1) return fail(VP_EINVAL, "kind must be 0 (vp_clip) or 1 (vp_classifier)");
+  WrapHandle* w = kind == 0 ? static_cast<WrapHandle*>(static_cast<vp_clip*>(handle))
+                            : static_cast<WrapHandle*>(static_cast<vp_classifier*>(handle));
+  if (!w->finalized) return fail(VP_ESTATE, "the handle has not been finalized");
+  if (G < 1 || S < 1 || G * S > 0x7fffffff) return fail(VP_EINVAL, "pooler: bad G or S");
+  const vp_config& v = w->video->cfg;
+  const int D = v.model_dim, NH = v.num_heads;
+  if (D % 256 || D > 1024) return fail(VP_ENOTSUP, "pooler kernels need model_dim % 256 == 0, at most 1024");
+  const DevPoolWs L = dev_pool_ws(G, S, D, NH, w->pool.dp);
+  if (!scratch) {
+    *scratch_bytes = L.total;
+    return VP_OK;
+  }
+  if (!feat || !dst) return fail(VP_EINVAL, "null argument");
+  if (*scratch_bytes < L.total) return fail(VP_EINVAL, "scratch too small: need " + std::to_string(L.total));
+  VP_HIP(hipSetDevice(w->device));
+  char* ws = static_cast<char*>(scratch);
+  auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  const PoolScratch sc{f32(L.logits), f32(L.stats), f32(L.zpart), f32(L.z), f32(L.enc), f32(L.pooled),
+                       (L.z - L.zpart) / 4};
+  Fwd f;
+  f.s = static_cast<hipStream_t>(stream); f.bf = w->bf16(); f.M = (int)(G * S); f.D = D; f.NH = NH;
+  return run_pooler(f, w->pool, feat, (int)(G * S), (int)G, (int)S, D, NH, sc, do_l2, dst);
 }
 
 }  // extern "C"

@@ -150,6 +150,22 @@ _SIGNATURES = {
                                   c_void_p, c_void_p, c_int64, c_float, c_void_p]),
     # which attention kernel the library picks (vpi::choose_attention); no GPU call
     "vp_dev_attention_choice": (c_int, [c_int, c_int, c_int64, c_float, c_int]),
+    # the pooler, small GEMM and text kernels one at a time (tests/test_gpu_clip_kernels.py)
+    "vp_dev_pool_split_u": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
+    "vp_dev_pool_chunks": (c_int, [c_int64]),
+    "vp_dev_pool_logits": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p]),
+    "vp_dev_pool_softmax_wsum": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p]),
+    "vp_dev_small_gemm": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                  c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                  c_void_p]),
+    "vp_dev_ln_l2_rows": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int,
+                                  c_void_p, c_void_p]),
+    "vp_dev_text_embed": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                  c_float, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vp_dev_pooler": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                              POINTER(c_size_t), c_void_p]),
 }
 # diag library only (ablation builds for tools/)
 _DIAG_SIGNATURES = {
@@ -362,6 +378,81 @@ def dev_ln_stats(src, M, D, out, from_partials, stream=None):
     """(rstd, -mean*rstd) per row from partial statistics (from_partials) or bf16 rows."""
     call("vp_dev_ln_stats", 0 if from_partials else 1, _ptr(src), M, D, _ptr(out), _stream(stream))
     return out
+
+
+# The pooler, small GEMM and text kernels one at a time.  The caller provides every output and scratch
+# tensor (contiguous, on the device), so a test can prefill them and see what a kernel leaves alone.
+def dev_pool_split_u(U):
+    """Host only: U [H, D] fp32 (NumPy) -> the logits kernel's bf16 operand [32, D] as uint16 bits,
+    rows (U_hi | U_lo | 0), packed by the function the engines' finalize calls."""
+    import numpy as np
+    U = np.ascontiguousarray(U, dtype=np.float32)
+    H, D = U.shape
+    ut = np.full((32, D), 0xFFFF, np.uint16)
+    call("vp_dev_pool_split_u", U.ctypes.data_as(c_void_p), H, D, ut.ctypes.data_as(c_void_p))
+    return ut
+
+
+def dev_pool_chunks(S) -> int:
+    """Row chunks the weighted sum splits S rows into (zpart is [G][chunks][H][D])."""
+    n = load().vp_dev_pool_chunks(S)
+    if n < 0:
+        raise ValueError(f"bad S {S}")
+    return n
+
+
+def dev_pool_logits(x, S, U, Ut, logits, stream=None):
+    """logits [rows/S][H][S] fp32 = x [rows, D] (fp32 / bf16) . U [H, D]; Ut: the uploaded split or None."""
+    rows, D = x.shape
+    call("vp_dev_pool_logits", _ptr(x), _prec(x), rows, S, D, _ptr(U), _ptr(Ut), U.shape[0], _ptr(logits),
+         _stream(stream))
+    return logits
+
+
+def dev_pool_softmax_wsum(x, G, S, H, logits, stats, zpart, z, stream=None):
+    """stats [G*H, 2] = (max, 1/sum exp), z [G, H, D] = softmax(logits [G, H, S]) . x [G*S, D]."""
+    call("vp_dev_pool_softmax_wsum", _ptr(x), _prec(x), G, S, x.shape[1], H, _ptr(logits), _ptr(stats), _ptr(zpart),
+         _ptr(z), _stream(stream))
+    return z
+
+
+def dev_small_gemm(A, lda, sA, Wt, sW, bias, sB, out, ldo, sO, M, N, K, batch=1, splits=0, part=None, stream=None):
+    """out[b][m][n] = A[b][m][:] . Wt[b][:][n] + bias[b][n] in fp32 (element strides); splits >= 1: the
+    split-K path (batch 1, part [splits][M][N])."""
+    call("vp_dev_small_gemm", _ptr(A), lda, sA, _ptr(Wt), sW, _ptr(bias), sB, _ptr(out), ldo, sO, M, N, K, batch,
+         splits, _ptr(part), _stream(stream))
+    return out
+
+
+def dev_ln_l2_rows(x, stride, rows, D, gamma1p, beta, do_l2, out, stream=None):
+    """out [rows, D] fp32 = LayerNorm (skipped if gamma1p is None) and / or L2 of rows x[r * stride : +D]."""
+    call("vp_dev_ln_l2_rows", _ptr(x), _prec(x), stride, rows, D, _ptr(gamma1p), _ptr(beta), 1 if do_l2 else 0,
+         _ptr(out), _stream(stream))
+    return out
+
+
+def dev_text_embed(ids, table, cls, pos, scale, out, pad_in, pad_out, stream=None):
+    """out [Q, L+1, D] = table[clamp(ids)] * scale + pos, CLS row appended; pad_out [Q, L+1] = [pad_in | 0]."""
+    Q, L = ids.shape
+    V, D = table.shape
+    call("vp_dev_text_embed", _ptr(ids), Q, L, _ptr(table), _prec(table), V, _ptr(cls), _ptr(pos), float(scale), D,
+         _ptr(out), _prec(out), _ptr(pad_in), _ptr(pad_out), _stream(stream))
+    return out
+
+
+def dev_pooler_scratch_bytes(kind, handle, G, S) -> int:
+    n = c_size_t()
+    call("vp_dev_pooler", kind, handle, None, G, S, 0, None, None, ctypes.byref(n), None)
+    return n.value
+
+
+def dev_pooler(kind, handle, feat, G, S, do_l2, dst, scratch, stream=None):
+    """The whole pooler of a finalized vp_clip (kind 0) / vp_classifier (kind 1) handle over tokens
+    feat [G*S, D] in the handle's fprop dtype -> dst [G, D] fp32; scratch: uint8, dev_pooler_scratch_bytes."""
+    n = c_size_t(scratch.numel())
+    call("vp_dev_pooler", kind, handle, _ptr(feat), G, S, 1 if do_l2 else 0, _ptr(dst), _ptr(scratch),
+         ctypes.byref(n), _stream(stream))
+    return dst
 
 
 # vp_dev_attention_choice: stack kinds (vp_internal.h AttnKind; ATT_OP: as vp_op_attention maps S and the key

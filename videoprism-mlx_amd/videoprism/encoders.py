@@ -103,6 +103,10 @@ class _EngineBase:
     def _create_args(self) -> tuple:
         raise NotImplementedError
 
+    def handle(self):
+        """The native handle itself (vp_handle / vp_clip / vp_classifier), for the _native.dev_* entries."""
+        return self._h
+
     def video_handle(self):
         """The vp_handle of the encoder (its profiler and positional tables live there)."""
         v = ctypes.c_void_p()
