@@ -40,8 +40,9 @@ def _merge(o, num_seq, S, heads):
     return o.reshape(num_seq, heads, S, 64).transpose(0, 2, 1, 3).reshape(num_seq * S, heads * 64)
 
 
-# scale 0.125 keeps every logit below 0.48*cap (one-transcendental polynomial numerator), the
-# larger scales put logits past it in most tiles (exact three-transcendental path)
+# scales 0.125 and 0.3 keep every ballot group (32 queries x 32 keys) below 0.10*cap: the linear tier only;
+# scale 1.0 is the exact three-transcendental form with a few cubic groups (248 of 6144 at S = 512, 1274 of 32768 at 4096);
+# 2.0 and 3.0 are the exact form throughout.  QUAD and cubic: tests/test_gpu_attention_tiers.py
 @pytest.mark.parametrize("S,num_seq,heads,scale", [(512, 2, 12, 1.0), (1024, 1, 3, 3.0),
                                                    (4096, 1, 2, 1.0), (768, 3, 16, 2.0),
                                                    (512, 2, 12, 0.125), (2048, 1, 4, 0.3)])

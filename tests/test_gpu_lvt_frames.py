@@ -8,8 +8,8 @@ partial last block of queries and keys (attention_long_kernel.h TAIL), or the se
 T*N <= 256.
 
   * kernel: attention_long_bf16 at S = 300 / 520 / 1000 / 3136 vs the oracle, per element within
-    2^-8 (|ref| + max|v|) (test_gpu_clip.py's bar for this kernel), at logit scales that take every
-    numerator tier;
+    2^-8 (|ref| + max|v|) (test_gpu_clip.py's bar for this kernel), at logit scales that take the linear
+    tier or the exact form (the tiers between: tests/test_gpu_attention_tiers.py);
   * kernel: bf16 attention with key paddings beyond 256 keys (the forward's attention_masked), S = 300
     and 520, random paddings and a fully padded sequence, through vp_op_attention and
     vp_op_attention_masked (causal and not);
@@ -59,7 +59,10 @@ def _merge(o, num_seq, S, heads):
     return o.reshape(num_seq, heads, S, 64).transpose(0, 2, 1, 3).reshape(num_seq * S, heads * 64)
 
 
-# scale 0.1 keeps the logits in the linear tier, 0.3 / 1 in the polynomial ones, 3 in the exact form
+# what these scales reach, counted per ballot group (32 queries x 32 keys): 0.1 and 0.3 keep every group in the
+# linear tier; 1.0 is the exact form with a few cubic groups (233 of 2400 at S = 300; 1 LIN, 3 QUAD, 74 cubic of 324 at
+# S = 257, the LIN and QUAD ones tail groups of 1 row or key); 2 and 3 are the exact form throughout.  The QUAD and cubic tiers are pinned by
+# tests/test_gpu_attention_tiers.py, not here
 @pytest.mark.parametrize("S,num_seq,heads,scale", [(300, 2, 12, 1.0), (520, 3, 4, 3.0), (1000, 1, 16, 0.1),
                                                    (3136, 1, 12, 0.3), (257, 2, 2, 1.0), (319, 1, 3, 2.0)])
 def test_attention_long_bf16_partial_blocks(cuda, S, num_seq, heads, scale):
