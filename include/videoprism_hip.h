@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define VP_ABI_VERSION 6
+#define VP_ABI_VERSION 7
 
 typedef struct vp_handle vp_handle;
 
@@ -62,10 +62,10 @@ typedef struct vp_config {
   int32_t pos_emb_t;           /* pos_emb_shape[0]: 16 (Base) / 8 (Large) */
   int32_t pos_emb_h;           /* pos_emb_shape[1]: 16 */
   int32_t pos_emb_w;           /* pos_emb_shape[2]: 16 */
-  int32_t model_dim;           /* 768 / 1024 */
+  int32_t model_dim;           /* 768 / 1024 / 1408 (VP_F32: a multiple of 128; VP_BF16: of 256) */
   int32_t num_spatial_layers;  /* 12 / 24 */
   int32_t num_temporal_layers; /* 4 */
-  int32_t num_heads;           /* 12 / 16 (dim_per_head must be 64) */
+  int32_t num_heads;           /* 12 / 16 (dim_per_head 64; 88 -- Giant, 1408 / 16 -- with fprop_dtype VP_F32 only) */
   int32_t mlp_dim;             /* 3072 / 4096 */
   float atten_logit_cap;       /* 50.0 */
   int32_t fprop_dtype;         /* VP_F32 (reference default) or VP_BF16 (get_model(fprop_dtype=bf16)) */
@@ -164,7 +164,16 @@ int vp_op_gemm(int precision, int epilogue, const void* A, int64_t lda, const vo
 int vp_op_attention(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S,
                     int64_t heads, float cap, const float* key_pad, void* stream);
 
-/* LayerNorm (layers.py:208-270) of fp32 or bf16 rows (in_dtype) with gamma = 1 + scale; optional
+/* vp_op_attention over heads of dim_per_head values: rows qkv[num_seq*S, 3*heads*dim_per_head], o[num_seq*S,
+ * heads*dim_per_head].  64 is vp_op_attention itself.  88 (the Giant encoder's 1408 / 16) runs in VP_F32 only,
+ * on the same fp32 kernels with one boundary moved: the fp32 kernel keeps K|V of a sequence in LDS, which
+ * 88-wide heads fill at S = 224, so with a cap outside (0, 50] sequences of 224 < S <= 256 take the
+ * online-softmax kernel.  Any other width, and 88 in VP_BF16, is VP_ENOTSUP. */
+int vp_op_attention_dh(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S, int64_t heads,
+                       int64_t dim_per_head, float cap, const float* key_pad, void* stream);
+
+/* LayerNorm (layers.py:208-270) of fp32 or bf16 rows (in_dtype) of D = 128 k values (k in 1..12, or 16; else
+ * VP_ENOTSUP) with gamma = 1 + scale; optional
  * row permutation (0 none, 1 (b t n)->(b n t), 2 (b n t)->(b t n)) and fp32 add[t][D] by output t. */
 int vp_op_layernorm(const void* x, int in_dtype, int64_t rows, int64_t D, const float* gamma,
                     const float* beta, void* out, int out_dtype, int perm, int64_t T, int64_t Nsp,
@@ -203,6 +212,10 @@ int vp_op_pool_l2(const void* emb, int dtype, int64_t B, int64_t L, int64_t D, f
  * online softmax. */
 int vp_op_attention_masked(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S,
                            int64_t heads, float cap, const float* key_pad, int causal, void* stream);
+
+/* vp_op_attention_masked over heads of dim_per_head values (64, or 88 in VP_F32; else VP_ENOTSUP). */
+int vp_op_attention_masked_dh(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S, int64_t heads,
+                              int64_t dim_per_head, float cap, const float* key_pad, int causal, void* stream);
 
 /* video_emb [B, D] . text_emb [Q, D]^T -> out [B, Q] (fp32): the video-text similarity of the
  * LvT models (README / colab usage of FactorizedVideoCLIP's embeddings). */

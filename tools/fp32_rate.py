@@ -1,6 +1,9 @@
 """Throughput of the fp32 forward (fprop_dtype=None: the reference's default precision, models.py:268-303):
-Base (or Large) at B clips x 16 x 288 x 288 on one GPU, with the per-class kernel breakdown from the
-library's HIP-event profiler.  Measurement only (the bench's headline is bf16)."""
+Base (or Large, or `giant`: videoprism_v1_giant, which has no checkpoint name) at B clips x 16 x 288 x 288 on one
+GPU, with the per-class kernel breakdown from the library's HIP-event profiler.  Measurement only (the bench's
+headline is bf16).
+
+  python tools/fp32_rate.py [videoprism_public_v1_base | videoprism_public_v1_large | giant] [B] [steps]"""
 import json
 import os
 import sys
@@ -15,9 +18,10 @@ from videoprism import models, params  # noqa: E402
 
 def main(name="videoprism_public_v1_base", B=4, steps=3):
     cfg_key = {"videoprism_public_v1_base": "videoprism_v1_base",
-               "videoprism_public_v1_large": "videoprism_v1_large"}[name]
+               "videoprism_public_v1_large": "videoprism_v1_large", "giant": "videoprism_v1_giant"}[name]
     cfg = dict(models.CONFIGS[cfg_key])
-    model = models.get_model(name)  # fp32
+    # fp32; Giant is in no checkpoint table (as in the reference), so it comes from its builder
+    model = models.get_model(None, model_fn=models.videoprism_v1_giant) if name == "giant" else models.get_model(name)
     var = params.synthetic_params(cfg, seed=0)
     eng = model.engine(var, 0)
     video = torch.rand((B, 16, 288, 288, 3), device="cuda:0")

@@ -30,6 +30,9 @@
 //   auxiliary, fp32  0 < cap <= 50: f32_mfma; otherwise masked
 //   auxiliary, bf16  S >= 256: long; S > 16: seq; otherwise temporal
 //   video, fp32      S <= 256: f32; longer: f32_mfma for 0 < cap <= 50, otherwise masked
+//                    (88-wide heads, cap outside (0, 50]: f32 up to S = 224, its LDS limit; longer: masked)
+// The fp32 kernels here take heads of 64 or 88 floats (template parameter DH; 88: the Giant encoder, 1408 / 16); the
+// bf16 kernels are 64-wide only.
 //   video, bf16      S == 256: spatial; S <= 16: temporal; S < 256: seq; longer: masked
 #include <type_traits>
 
@@ -546,26 +549,30 @@ __global__ __launch_bounds__(kTpWaves * 64) void attn_temporal_kernel(
 // ------------------------------------------------------------------------------------
 constexpr int kF32MaxS = 256;
 
+// DH: head width, 64 or 88 (the Giant encoder's 1408 / 16).  K|V of the sequence take 8 S DH bytes of LDS, so
+// the longest sequence is f32_generic_max_s(DH) (vp_kernels.h): 256 at 64, 224 at 88 (158.6 KB of the CU's 160 KiB)
+template <int DH>
 __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__ qkv,
                                                         float* __restrict__ o, int S, int heads,
                                                         float cap,
                                                         const float* __restrict__ key_pad) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* Ks = reinterpret_cast<float*>(smem);        // [S][64]
-  float* Vs = Ks + S * 64;                            // [S][64]
-  float* kp = Vs + S * 64;                            // [S]
+  constexpr int C4 = DH / 4;  // float4 per head row
+  float* Ks = reinterpret_cast<float*>(smem);        // [S][DH]
+  float* Vs = Ks + S * DH;                            // [S][DH]
+  float* kp = Vs + S * DH;                            // [S]
   int& nvalid = *reinterpret_cast<int*>(kp + S);
-  const int D = heads * 64;
+  const int D = heads * DH;
   const int64_t ld = 3 * (int64_t)D;
   const int seq = blockIdx.x / heads;
   const int h = blockIdx.x % heads;
-  const float* base = qkv + (int64_t)seq * S * ld + h * 64;
+  const float* base = qkv + (int64_t)seq * S * ld + h * DH;
   if (threadIdx.x == 0) nvalid = 0;
-  for (int i = threadIdx.x; i < S * 16; i += blockDim.x) {
-    const int row = i >> 4, c4 = (i & 15) * 4;
-    *reinterpret_cast<float4*>(Ks + row * 64 + c4) =
+  for (int i = threadIdx.x; i < S * C4; i += blockDim.x) {
+    const int row = DH == 64 ? i >> 4 : i / C4, c4 = (DH == 64 ? i & 15 : i % C4) * 4;
+    *reinterpret_cast<float4*>(Ks + row * DH + c4) =
         *reinterpret_cast<const float4*>(base + (int64_t)row * ld + D + c4);
-    *reinterpret_cast<float4*>(Vs + row * 64 + c4) =
+    *reinterpret_cast<float4*>(Vs + row * DH + c4) =
         *reinterpret_cast<const float4*>(base + (int64_t)row * ld + 2 * D + c4);
   }
   __syncthreads();
@@ -578,22 +585,22 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
   const bool all_masked = nvalid == 0;
   const int qi = threadIdx.x;
   if (qi >= S) return;
-  float q[64];
+  float q[DH];
 #pragma unroll
-  for (int d = 0; d < 64; d += 4) {
+  for (int d = 0; d < DH; d += 4) {
     const float4 t = *reinterpret_cast<const float4*>(base + (int64_t)qi * ld + d);
     q[d] = t.x; q[d + 1] = t.y; q[d + 2] = t.z; q[d + 3] = t.w;
   }
-  float acc[64];
+  float acc[DH];
 #pragma unroll
-  for (int d = 0; d < 64; ++d) acc[d] = 0.f;
+  for (int d = 0; d < DH; ++d) acc[d] = 0.f;
   float m = -INFINITY, l = 0.f;
   for (int j = 0; j < S; ++j) {
     if (!all_masked && kp[j] != 0.0f) continue;
     float s = 0.f;
     if (!all_masked) {
 #pragma unroll
-      for (int d = 0; d < 64; ++d) s = fmaf(q[d], Ks[j * 64 + d], s);
+      for (int d = 0; d < DH; ++d) s = fmaf(q[d], Ks[j * DH + d], s);
       if (cap > 0.f) s = cap * tanhf(s / cap);
     }
     const float mn = fmaxf(m, s);
@@ -601,13 +608,13 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
     const float e = expf(s - mn);
     l = l * sc + e;
 #pragma unroll
-    for (int d = 0; d < 64; ++d) acc[d] = fmaf(acc[d], sc, e * Vs[j * 64 + d]);
+    for (int d = 0; d < DH; ++d) acc[d] = fmaf(acc[d], sc, e * Vs[j * DH + d]);
     m = mn;
   }
   const float inv = 1.0f / l;
-  float* op = o + ((int64_t)seq * S + qi) * D + h * 64;
+  float* op = o + ((int64_t)seq * S + qi) * D + h * DH;
 #pragma unroll
-  for (int d = 0; d < 64; d += 4)
+  for (int d = 0; d < DH; d += 4)
     *reinterpret_cast<float4*>(op + d) =
         make_float4(acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv);
 }
@@ -629,6 +636,14 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
 // V operands are one 8-byte read.  Padded keys (MASK) weigh 0, a fully padded sequence gives uniform weights
 // (as attn_f32_kernel); TAIL (S % 256 != 0): query and key rows past S read row S - 1, keys past S weigh 0,
 // queries past S are not stored.
+// DH = 88 (the Giant encoder's heads, 1408 / 16): the contraction splits 44 + 44 over the lane halves (11 b128
+// K reads per tile instead of 8) and O^T gets a third 32-row block for d = 64 + i, read one float per lane;
+// its rows 24..31 (d = 88..95) are dead: those lanes re-read column 87 (nothing past the head row is read) and
+// the rows are never stored.  Rows are padded to 92 floats (23 16-B slots, odd as 17 is, so the 16 key rows of
+// a b128 lane group fall on 16 different slots; the b64 / b32 V reads of a lane half are one contiguous run of
+// at most 256 B at any pitch).  128-key chunks of 92-float rows would take 189 KB double-buffered, more than
+// the CU's 160 KiB, so DH = 88 streams 64-key chunks: 2 x (2 x 64 x 92 + 64) x 4 = 94.7 KB, chunks that divide
+// S = 256 (the non-TAIL variants need that) at twice the barriers per key.
 // ------------------------------------------------------------------------------------
 // exp(cap * tanh(x / cap)) in fp32 for the 16 logits of a 32x32 tile (the MFMA kernel's numerators), accurate
 // to a few fp32 ulp without the libm calls (≈ 14 VALU operations and one transcendental per logit instead of ≈ 56):
@@ -673,33 +688,45 @@ __device__ __forceinline__ void capped_exp_f32x16(const f32x16& x, float* e, flo
   }
 }
 
-constexpr int kF32Chunk = 128, kF32Row = 68;
-constexpr int kF32BufFloats = 2 * kF32Chunk * kF32Row + kF32Chunk;  // K, V, key paddings of one chunk
-constexpr int kF32MfmaLds = 2 * kF32BufFloats * 4 + 16;
+// chunk and row geometry of attn_f32_mfma_kernel for head width DH
+template <int DH>
+struct F32Mfma {
+  static_assert(DH == 64 || DH == 88, "head width");
+  static constexpr int kChunk = DH == 64 ? 128 : 64, kRow = DH + 4;
+  static constexpr int kBufFloats = 2 * kChunk * kRow + kChunk;  // K, V, key paddings of one chunk
+  static constexpr int kLds = 2 * kBufFloats * 4 + 16;
+  static constexpr int kHalf = DH / 2;                           // contraction steps per lane half
+  static constexpr int kC4 = DH / 4;                             // float4 per head row
+  static constexpr int kVec = kChunk * kC4;                      // float4 of K (and of V) per chunk
+  static constexpr int kStage = (kVec + 511) / 512;              // ... per thread
+};
 
-template <bool MASK, bool TAIL>
+template <int DH, bool MASK, bool TAIL>
 __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restrict__ qkv, float* __restrict__ o,
                                                             int S, int heads, int nqb, float cap,
                                                             const float* __restrict__ key_pad) {
+  using G = F32Mfma<DH>;
+  constexpr int kF32Chunk = G::kChunk, kF32Row = G::kRow, kF32BufFloats = G::kBufFloats;
+  constexpr bool kWhole = G::kVec % 512 == 0;  // every thread stages kStage float4 (else the last round is partial)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* bufs = reinterpret_cast<float*>(smem);
-  const int D = heads * 64;
+  const int D = heads * DH;
   const int64_t ld = 3 * (int64_t)D;
   const int qb = blockIdx.x % nqb;
   const int sh = blockIdx.x / nqb;
   const int seq = sh / heads;
   const int h = sh % heads;
-  const float* base = qkv + (int64_t)seq * S * ld + h * 64;
+  const float* base = qkv + (int64_t)seq * S * ld + h * DH;
   const int t = threadIdx.x, lane = t & 63, w = wave_id();
   const int half = lane >> 5, l32 = lane & 31;
   const int q = qb * 256 + 32 * w + l32;
 
-  // this wave's 32 queries as the B operand: lane l holds Q[q][32 (l / 32) + s], s = 0..31
-  float qf[32];
+  // this wave's 32 queries as the B operand: lane l holds Q[q][kHalf (l / 32) + s], s = 0..kHalf-1
+  float qf[G::kHalf];
   {
-    const float* qp = base + (int64_t)(TAIL ? min(q, S - 1) : q) * ld + 32 * half;
+    const float* qp = base + (int64_t)(TAIL ? min(q, S - 1) : q) * ld + G::kHalf * half;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < G::kHalf / 4; ++i) {
       const float4 v = *reinterpret_cast<const float4*>(qp + 4 * i);
       qf[4 * i] = v.x; qf[4 * i + 1] = v.y; qf[4 * i + 2] = v.z; qf[4 * i + 3] = v.w;
     }
@@ -710,16 +737,18 @@ __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restr
     for (int i = t; i < S; i += 512) valid |= key_pad[(int64_t)seq * S + i] == 0.0f;
     all_masked = __syncthreads_or(valid) == 0;
   }
-  // chunk c: 128 key rows x 16 float4 of K and of V, 4 of each per thread (+ the chunk's key paddings)
-  f32x4 kr[4], vr[4];  // (native vectors: arrays of HIP's float4 struct stay in scratch here)
+  // chunk c: kChunk key rows x kC4 float4 of K and of V, kStage of each per thread (+ the chunk's key paddings)
+  f32x4 kr[G::kStage], vr[G::kStage];  // (native vectors: arrays of HIP's float4 struct stay in scratch here)
   float pr = 0.0f;
   auto stage = [&](int c) __attribute__((always_inline)) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = t + 512 * i, row = idx >> 4, c4 = (idx & 15) * 4;
-      const int key = TAIL ? min(c * kF32Chunk + row, S - 1) : c * kF32Chunk + row;
-      kr[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)key * ld + D + c4);
-      vr[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)key * ld + 2 * D + c4);
+    for (int i = 0; i < G::kStage; ++i) {
+      const int idx = t + 512 * i, row = idx / G::kC4, c4 = (idx % G::kC4) * 4;
+      if (kWhole || idx < G::kVec) {
+        const int key = TAIL ? min(c * kF32Chunk + row, S - 1) : c * kF32Chunk + row;
+        kr[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)key * ld + D + c4);
+        vr[i] = *reinterpret_cast<const f32x4*>(base + (int64_t)key * ld + 2 * D + c4);
+      }
     }
     if constexpr (MASK) {
       const int key = c * kF32Chunk + t;
@@ -730,17 +759,22 @@ __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restr
     float* Kb = bufs + (c & 1) * kF32BufFloats;
     float* Vb = Kb + kF32Chunk * kF32Row;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = t + 512 * i, row = idx >> 4, c4 = (idx & 15) * 4;
-      *reinterpret_cast<f32x4*>(Kb + row * kF32Row + c4) = kr[i];
-      *reinterpret_cast<f32x4*>(Vb + row * kF32Row + c4) = vr[i];
+    for (int i = 0; i < G::kStage; ++i) {
+      const int idx = t + 512 * i, row = idx / G::kC4, c4 = (idx % G::kC4) * 4;
+      if (kWhole || idx < G::kVec) {
+        *reinterpret_cast<f32x4*>(Kb + row * kF32Row + c4) = kr[i];
+        *reinterpret_cast<f32x4*>(Vb + row * kF32Row + c4) = vr[i];
+      }
     }
     if constexpr (MASK) {
       if (t < kF32Chunk) Vb[kF32Chunk * kF32Row + t] = pr;
     }
   };
 
-  f32x16 y0 = {}, y1 = {};  // O^T blocks b = 0 / 1: row i <-> d = 2 i + b
+  // O^T blocks b = 0 / 1: row i <-> d = 2 i + b; DH = 88: block 2, row i <-> d = 64 + i (rows 24..31 dead)
+  f32x16 y0 = {}, y1 = {};
+  [[maybe_unused]] f32x16 y2 = {};
+  [[maybe_unused]] const int v2col = 64 + (l32 < DH - 64 ? l32 : DH - 65);
   float lsum = 0.0f;
   const float inv_cap = 1.0f / cap;
   const int nch = (S + kF32Chunk - 1) / kF32Chunk;
@@ -755,11 +789,11 @@ __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restr
     const float* kp = Vb + kF32Chunk * kF32Row;
 #pragma unroll 1
     for (int kt = 0; kt < kF32Chunk / 32; ++kt) {
-      // S^T tile: x[r] = logit(key c 128 + kt 32 + 8 (r / 4) + 4 half + r % 4, query q)
+      // S^T tile: x[r] = logit(key c kChunk + kt 32 + 8 (r / 4) + 4 half + r % 4, query q)
       f32x16 x = {};
-      const float* kq = Kb + (kt * 32 + l32) * kF32Row + 32 * half;
+      const float* kq = Kb + (kt * 32 + l32) * kF32Row + G::kHalf * half;
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
+      for (int i = 0; i < G::kHalf / 4; ++i) {
         const float4 kv = *reinterpret_cast<const float4*>(kq + 4 * i);
         x = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.x, qf[4 * i], x, 0, 0, 0);
         x = __builtin_amdgcn_mfma_f32_32x32x2f32(kv.y, qf[4 * i + 1], x, 0, 0, 0);
@@ -778,6 +812,7 @@ __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restr
         const float2 vv = *reinterpret_cast<const float2*>(Vb + kl * kF32Row + 2 * l32);
         y0 = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.x, e, y0, 0, 0, 0);
         y1 = __builtin_amdgcn_mfma_f32_32x32x2f32(vv.y, e, y1, 0, 0, 0);
+        if constexpr (DH > 64) y2 = __builtin_amdgcn_mfma_f32_32x32x2f32(Vb[kl * kF32Row + v2col], e, y2, 0, 0, 0);
       }
     }
     // buffer (c + 1) & 1 was last read in chunk c - 1, before the previous barrier
@@ -788,13 +823,21 @@ __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restr
   const float inv = 1.0f / lsum;
   if (TAIL && q >= S) return;
   // y_b[4 m + c] = O[q][d = 16 m + 8 half + 2 c + b]: 8 consecutive floats per m
-  float* op = o + ((int64_t)seq * S + q) * D + h * 64 + 8 * half;
+  float* op = o + ((int64_t)seq * S + q) * D + h * DH + 8 * half;
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
     *reinterpret_cast<float4*>(op + 16 * m) =
         make_float4(y0[4 * m] * inv, y1[4 * m] * inv, y0[4 * m + 1] * inv, y1[4 * m + 1] * inv);
     *reinterpret_cast<float4*>(op + 16 * m + 4) =
         make_float4(y0[4 * m + 2] * inv, y1[4 * m + 2] * inv, y0[4 * m + 3] * inv, y1[4 * m + 3] * inv);
+  }
+  if constexpr (DH > 64) {
+    // y2[4 m + c] = O[q][d = 64 + 8 m + 4 half + c]: the live rows are m < (DH - 64) / 8
+    float* op2 = o + ((int64_t)seq * S + q) * D + h * DH + 64 + 4 * half;
+#pragma unroll
+    for (int m = 0; m < (DH - 64) / 8; ++m)
+      *reinterpret_cast<float4*>(op2 + 8 * m) =
+          make_float4(y2[4 * m] * inv, y2[4 * m + 1] * inv, y2[4 * m + 2] * inv, y2[4 * m + 3] * inv);
   }
 }
 
@@ -867,21 +910,23 @@ hipError_t attention_seq_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S, 
   return hipGetLastError();
 }
 
-hipError_t attention_f32_mfma(const float* qkv, float* o, int num_seq, int S, int heads, float cap,
-                              const float* key_pad, hipStream_t s) {
-  if (!(cap > 0.0f && cap <= 50.0f)) return hipErrorNotSupported;
-  if (S < 1 || num_seq < 1 || heads < 1) return hipErrorInvalidValue;
+namespace {
+
+template <int DH>
+hipError_t launch_f32_mfma(const float* qkv, float* o, int num_seq, int S, int heads, float cap, const float* key_pad,
+                           hipStream_t s) {
+  constexpr int kLds = F32Mfma<DH>::kLds;
   const int nqb = (S + 255) / 256;
   const int64_t grid = (int64_t)num_seq * heads * nqb;
   if (grid > 0x7fffffff || (int64_t)num_seq * S > 0x7fffffff) return hipErrorInvalidValue;
   const int mi = (key_pad ? 1 : 0) + (S % 256 ? 2 : 0);
-  const void* fns[4] = {(const void*)attn_f32_mfma_kernel<false, false>, (const void*)attn_f32_mfma_kernel<true, false>,
-                        (const void*)attn_f32_mfma_kernel<false, true>, (const void*)attn_f32_mfma_kernel<true, true>};
-  hipError_t e = ensure_dyn_lds(fns[mi], kF32MfmaLds);
+  const void* fns[4] = {(const void*)attn_f32_mfma_kernel<DH, false, false>, (const void*)attn_f32_mfma_kernel<DH, true, false>,
+                        (const void*)attn_f32_mfma_kernel<DH, false, true>, (const void*)attn_f32_mfma_kernel<DH, true, true>};
+  hipError_t e = ensure_dyn_lds(fns[mi], kLds);
   if (e != hipSuccess) return e;
   VP_NOTE_KERNEL(fns[mi]);
 #define VP_F32M(M, T)                                                                                              \
-  hipLaunchKernelGGL((attn_f32_mfma_kernel<M, T>), dim3((unsigned)grid), dim3(512), kF32MfmaLds, s, qkv, o, S, heads, \
+  hipLaunchKernelGGL((attn_f32_mfma_kernel<DH, M, T>), dim3((unsigned)grid), dim3(512), kLds, s, qkv, o, S, heads, \
                      nqb, cap, key_pad)
   switch (mi) {
     case 0: VP_F32M(false, false); break;
@@ -893,19 +938,38 @@ hipError_t attention_f32_mfma(const float* qkv, float* o, int num_seq, int S, in
   return hipGetLastError();
 }
 
+template <int DH>
+hipError_t launch_f32_generic(const float* qkv, float* o, int num_seq, int S, int heads, float cap,
+                              const float* key_pad, hipStream_t s) {
+  constexpr int kMaxS = f32_generic_max_s(DH);
+  const int lds = (2 * S * DH + S) * 4 + 16;
+  hipError_t e = ensure_dyn_lds((const void*)attn_f32_kernel<DH>, (2 * kMaxS * DH + kMaxS) * 4 + 16);
+  if (e != hipSuccess) return e;
+  VP_NOTE_KERNEL(attn_f32_kernel<DH>);
+  hipLaunchKernelGGL(attn_f32_kernel<DH>, dim3(num_seq * heads), dim3(256), lds, s, qkv, o, S, heads, cap, key_pad);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t attention_f32_mfma(const float* qkv, float* o, int num_seq, int S, int heads, float cap,
+                              const float* key_pad, hipStream_t s, int dh) {
+  if (!(cap > 0.0f && cap <= 50.0f)) return hipErrorNotSupported;
+  if (S < 1 || num_seq < 1 || heads < 1 || (dh != 64 && dh != 88)) return hipErrorInvalidValue;
+  if (dh == 88) return launch_f32_mfma<88>(qkv, o, num_seq, S, heads, cap, key_pad, s);
+  return launch_f32_mfma<64>(qkv, o, num_seq, S, heads, cap, key_pad, s);
+}
+
 hipError_t attention_f32(const float* qkv, float* o, int num_seq, int S, int heads, float cap,
-                         const float* key_pad, hipStream_t s) {
-  if (S < 1 || S > kF32MaxS) return hipErrorInvalidValue;
+                         const float* key_pad, hipStream_t s, int dh) {
+  if (S < 1 || S > kF32MaxS || (dh != 64 && dh != 88)) return hipErrorInvalidValue;
   if (S >= 128) {  // MFMA kernel (max-free softmax: 0 < cap <= 50); other caps fall through to the generic one
-    const hipError_t e = attention_f32_mfma(qkv, o, num_seq, S, heads, cap, key_pad, s);
+    const hipError_t e = attention_f32_mfma(qkv, o, num_seq, S, heads, cap, key_pad, s, dh);
     if (e != hipErrorNotSupported) return e;
   }
-  const int lds = (2 * S * 64 + S) * 4 + 16;
-  hipError_t e = ensure_dyn_lds((const void*)attn_f32_kernel, (2 * kF32MaxS * 64 + kF32MaxS) * 4 + 16);
-  if (e != hipSuccess) return e;
-  VP_NOTE_KERNEL(attn_f32_kernel);
-  hipLaunchKernelGGL(attn_f32_kernel, dim3(num_seq * heads), dim3(256), lds, s, qkv, o, S, heads, cap, key_pad);
-  return hipGetLastError();
+  if (S > f32_generic_max_s(dh)) return hipErrorInvalidValue;  // K|V past the LDS (choose_attention: masked)
+  if (dh == 88) return launch_f32_generic<88>(qkv, o, num_seq, S, heads, cap, key_pad, s);
+  return launch_f32_generic<64>(qkv, o, num_seq, S, heads, cap, key_pad, s);
 }
 
 }  // namespace vp

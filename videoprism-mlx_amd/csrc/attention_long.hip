@@ -25,7 +25,7 @@ namespace vp {
 namespace {
 
 // ------------------------------------------------------------------------------------
-// generic masked attention, fp32 math (dh = 64)
+// generic masked attention, fp32 math (DH = 64, or 88 in fp32: each query's 4 lanes hold DH / 4 values)
 // ------------------------------------------------------------------------------------
 constexpr int kGnQ = 64;      // queries per workgroup (4 lanes each)
 constexpr int kGnChunk = 64;  // keys per LDS stage
@@ -36,28 +36,29 @@ __device__ __forceinline__ float ld_f(const T* p, int64_t i) {
   else return reinterpret_cast<const float*>(p)[i];
 }
 
-template <typename T>
+template <typename T, int DH = 64>
 __global__ __launch_bounds__(256) void attn_masked_kernel(const T* __restrict__ qkv, T* __restrict__ o, int S,
                                                          int heads, int nqb, float cap,
                                                          const float* __restrict__ key_pad, int causal) {
-  __shared__ float Ks[kGnChunk][65];
-  __shared__ float Vs[kGnChunk][64];
+  constexpr int DP = DH / 4;  // values per lane
+  __shared__ float Ks[kGnChunk][DH + 1];
+  __shared__ float Vs[kGnChunk][DH];
   __shared__ float kp[kGnChunk];
   __shared__ int any_valid_key;
   const int qb = blockIdx.x % nqb;
   const int sh = blockIdx.x / nqb;
   const int seq = sh / heads;
   const int h = sh % heads;
-  const int D = heads * 64;
+  const int D = heads * DH;
   const int64_t ld = 3 * (int64_t)D;
-  const T* base = qkv + (int64_t)seq * S * ld + h * 64;
+  const T* base = qkv + (int64_t)seq * S * ld + h * DH;
   const int t = threadIdx.x;
   const int qi = qb * kGnQ + (t >> 2);
   const int part = t & 3;
   const bool qvalid = qi < S;
-  float q[16];
+  float q[DP];
 #pragma unroll
-  for (int j = 0; j < 16; ++j) q[j] = qvalid ? ld_f(base, (int64_t)qi * ld + 16 * part + j) : 0.0f;
+  for (int j = 0; j < DP; ++j) q[j] = qvalid ? ld_f(base, (int64_t)qi * ld + DP * part + j) : 0.0f;
   // rows whose every key is masked get uniform weights (equal logits)
   if (t == 0) any_valid_key = 0;
   __syncthreads();
@@ -72,14 +73,14 @@ __global__ __launch_bounds__(256) void attn_masked_kernel(const T* __restrict__ 
     else all_masked = any_valid_key == 0;
   }
   float m = -INFINITY, l = 0.0f;
-  float acc[16];
+  float acc[DP];
 #pragma unroll
-  for (int j = 0; j < 16; ++j) acc[j] = 0.0f;
+  for (int j = 0; j < DP; ++j) acc[j] = 0.0f;
   // every thread runs the same key loop (barriers inside); masked keys are skipped per query
   for (int k0 = 0; k0 < S; k0 += kGnChunk) {
     __syncthreads();
-    for (int i = t; i < kGnChunk * 64; i += 256) {
-      const int r = i >> 6, d = i & 63;
+    for (int i = t; i < kGnChunk * DH; i += 256) {
+      const int r = i / DH, d = i % DH;
       const bool in = k0 + r < S;
       Ks[r][d] = in ? ld_f(base, (int64_t)(k0 + r) * ld + D + d) : 0.0f;
       Vs[r][d] = in ? ld_f(base, (int64_t)(k0 + r) * ld + 2 * D + d) : 0.0f;
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256) void attn_masked_kernel(const T* __restrict__ 
     for (int j = 0; j < n; ++j) {
       float d = 0.0f;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) d = fmaf(q[e], Ks[j][16 * part + e], d);
+      for (int e = 0; e < DP; ++e) d = fmaf(q[e], Ks[j][DP * part + e], d);
       d += __shfl_xor(d, 1);
       d += __shfl_xor(d, 2);
       const int key = k0 + j;
@@ -106,15 +107,15 @@ __global__ __launch_bounds__(256) void attn_masked_kernel(const T* __restrict__ 
       const float pe = __expf(logit - mn);
       l = l * sc + pe;
 #pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = fmaf(pe, Vs[j][16 * part + e], acc[e] * sc);
+      for (int e = 0; e < DP; ++e) acc[e] = fmaf(pe, Vs[j][DP * part + e], acc[e] * sc);
       m = mn;
     }
   }
   if (!qvalid) return;
   const float inv = 1.0f / l;
-  T* op = o + ((int64_t)seq * S + qi) * D + h * 64 + 16 * part;
+  T* op = o + ((int64_t)seq * S + qi) * D + h * DH + DP * part;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) {
+  for (int e = 0; e < DP; ++e) {
     const float v = acc[e] * inv;
     if constexpr (sizeof(T) == 2) reinterpret_cast<bf16_t*>(op)[e] = f2bf(v);
     else reinterpret_cast<float*>(op)[e] = v;
@@ -129,11 +130,18 @@ hipError_t attention_long_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S,
 }
 
 hipError_t attention_masked(const void* qkv, void* o, int in_is_bf16, int num_seq, int S, int heads,
-                            float cap, const float* key_pad, int causal, hipStream_t s) {
+                            float cap, const float* key_pad, int causal, hipStream_t s, int dh) {
   if (S < 1 || num_seq < 1) return hipErrorInvalidValue;
+  if (dh != 64 && !(dh == 88 && !in_is_bf16)) return hipErrorInvalidValue;
   const int nqb = (S + kGnQ - 1) / kGnQ;
   const int64_t grid = (int64_t)num_seq * heads * nqb;
   if (grid > 0x7fffffff) return hipErrorInvalidValue;
+  if (dh == 88) {
+    VP_NOTE_KERNEL((attn_masked_kernel<float, 88>));
+    hipLaunchKernelGGL((attn_masked_kernel<float, 88>), dim3((unsigned)grid), dim3(256), 0, s, (const float*)qkv,
+                       (float*)o, S, heads, nqb, cap, key_pad, causal);
+    return hipGetLastError();
+  }
   VP_NOTE_KERNEL(in_is_bf16 ? (const void*)attn_masked_kernel<bf16_t> : (const void*)attn_masked_kernel<float>);
   if (in_is_bf16)
     hipLaunchKernelGGL(attn_masked_kernel<bf16_t>, dim3((unsigned)grid), dim3(256), 0, s,

@@ -118,24 +118,34 @@ __global__ __launch_bounds__(256) void patchify_band_kernel(const TI* __restrict
 // ---- LayerNorm (layers.py:208-270) over fp32 or bf16 rows ----
 // One wave owns RPW rows: all RPW x NCH loads are issued before the first reduction (memory-level
 // parallelism for an HBM-bound kernel), and the RPW row reductions interleave.  NCH = D / 256
-// 4-element chunks per lane.  gamma = 1 + scale (folded on the host).
-template <int NCH, bool OUT_BF16, bool IN_BF16, int RPW>
+// 4-element chunks per lane.  gamma = 1 + scale (folded on the host).  HALF: D = NCH * 256 - 128 (1408 = 11 x 128,
+// the Giant encoder): the last chunk lives on lanes 0..31 only; the other lanes hold zeros there, which the
+// sums take as they are and the centred second pass puts back after subtracting the mean.
+template <int NCH, bool OUT_BF16, bool IN_BF16, int RPW, bool HALF = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__ x, int rows,
                                                         const float* __restrict__ gamma,
                                                         const float* __restrict__ beta,
                                                         void* __restrict__ out, int perm, int T,
                                                         int Nsp, const float* __restrict__ add,
                                                         float* __restrict__ out_rs) {
-  constexpr int D = NCH * 256;
+  constexpr int D = NCH * 256 - (HALF ? 128 : 0);
   const int lane = threadIdx.x & 63;
   const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
   if (row0 >= rows) return;
+  // HALF: this lane's last chunk lies past the row
+  [[maybe_unused]] const bool dead = HALF && lane >= 32;
   float4 v[RPW][NCH];
 #pragma unroll
   for (int r = 0; r < RPW; ++r) {
     const int row = row0 + r < rows ? row0 + r : rows - 1;  // tail rows: recomputed, not stored
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
+      if constexpr (HALF) {
+        if (c == NCH - 1 && dead) {
+          v[r][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+          continue;
+        }
+      }
       if constexpr (IN_BF16) {
         const uint2 u = *reinterpret_cast<const uint2*>(static_cast<const bf16_t*>(x) + (int64_t)row * D +
                                                         c * 256 + lane * 4);
@@ -166,6 +176,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       v[r][c].x -= mean; v[r][c].y -= mean; v[r][c].z -= mean; v[r][c].w -= mean;
+      if constexpr (HALF) {
+        if (c == NCH - 1 && dead) v[r][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
       ss[r] += (v[r][c].x * v[r][c].x + v[r][c].y * v[r][c].y) + (v[r][c].z * v[r][c].z + v[r][c].w * v[r][c].w);
     }
   }
@@ -177,6 +190,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
   float4 gm[NCH], bt[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
+    if constexpr (HALF) {
+      if (c == NCH - 1 && dead) {
+        gm[c] = bt[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+    }
     gm[c] = *reinterpret_cast<const float4*>(gamma + c * 256 + lane * 4);
     bt[c] = *reinterpret_cast<const float4*>(beta + c * 256 + lane * 4);
   }
@@ -204,6 +223,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
       const int col = c * 256 + lane * 4;
+      if constexpr (HALF) {
+        if (c == NCH - 1 && dead) {
+          ys[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+          continue;
+        }
+      }
       float4 y = make_float4(v[r][c].x * rstd * gm[c].x + bt[c].x, v[r][c].y * rstd * gm[c].y + bt[c].y,
                              v[r][c].z * rstd * gm[c].z + bt[c].z, v[r][c].w * rstd * gm[c].w + bt[c].w);
       if (add) {
@@ -231,6 +256,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const float dx = ys[c].x - mean, dy = ys[c].y - mean, dz = ys[c].z - mean, dw = ys[c].w - mean;
+        if constexpr (HALF) {
+          if (c == NCH - 1 && dead) continue;
+        }
         q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
       }
 #pragma unroll
@@ -407,7 +435,7 @@ int grid_for(int64_t work, int block) {
   return (int)g;
 }
 
-template <int NCH>
+template <int NCH, bool HALF = false>
 hipError_t ln_launch(const void* x, int in_is_bf16, int rows, const float* gamma, const float* beta,
                      void* out, int out_is_bf16, int perm, int T, int Nsp, const float* add, hipStream_t s,
                      float* out_rs) {
@@ -415,17 +443,17 @@ hipError_t ln_launch(const void* x, int in_is_bf16, int rows, const float* gamma
   const dim3 grid((rows + 4 * RPW - 1) / (4 * RPW));
   if (in_is_bf16) {
     if (out_is_bf16)
-      hipLaunchKernelGGL((layernorm_kernel<NCH, true, true, RPW>), grid, dim3(256), 0, s, x, rows, gamma, beta,
+      hipLaunchKernelGGL((layernorm_kernel<NCH, true, true, RPW, HALF>), grid, dim3(256), 0, s, x, rows, gamma, beta,
                          out, perm, T, Nsp, add, out_rs);
     else
-      hipLaunchKernelGGL((layernorm_kernel<NCH, false, true, RPW>), grid, dim3(256), 0, s, x, rows, gamma, beta,
+      hipLaunchKernelGGL((layernorm_kernel<NCH, false, true, RPW, HALF>), grid, dim3(256), 0, s, x, rows, gamma, beta,
                          out, perm, T, Nsp, add, out_rs);
   } else {
     if (out_is_bf16)
-      hipLaunchKernelGGL((layernorm_kernel<NCH, true, false, RPW>), grid, dim3(256), 0, s, x, rows, gamma, beta,
+      hipLaunchKernelGGL((layernorm_kernel<NCH, true, false, RPW, HALF>), grid, dim3(256), 0, s, x, rows, gamma, beta,
                          out, perm, T, Nsp, add, out_rs);
     else
-      hipLaunchKernelGGL((layernorm_kernel<NCH, false, false, RPW>), grid, dim3(256), 0, s, x, rows, gamma, beta,
+      hipLaunchKernelGGL((layernorm_kernel<NCH, false, false, RPW, HALF>), grid, dim3(256), 0, s, x, rows, gamma, beta,
                          out, perm, T, Nsp, add, out_rs);
   }
   return hipGetLastError();
@@ -468,15 +496,24 @@ hipError_t patchify(const void* video, int in_dtype, void* patches, int out_is_b
 hipError_t layernorm(const void* x, int in_is_bf16, int rows, int D, const float* gamma,
                      const float* beta, void* out, int out_is_bf16, int perm, int T, int Nsp,
                      const float* add, hipStream_t s, float* out_rs) {
-  switch (D) {
-    case 256: return ln_launch<1>(x, in_is_bf16, rows, gamma, beta, out, out_is_bf16, perm, T, Nsp, add, s, out_rs);
-    case 512: return ln_launch<2>(x, in_is_bf16, rows, gamma, beta, out, out_is_bf16, perm, T, Nsp, add, s, out_rs);
-    case 768: return ln_launch<3>(x, in_is_bf16, rows, gamma, beta, out, out_is_bf16, perm, T, Nsp, add, s, out_rs);
-    case 1024: return ln_launch<4>(x, in_is_bf16, rows, gamma, beta, out, out_is_bf16, perm, T, Nsp, add, s, out_rs);
-    case 1280: return ln_launch<5>(x, in_is_bf16, rows, gamma, beta, out, out_is_bf16, perm, T, Nsp, add, s, out_rs);
-    case 1536: return ln_launch<6>(x, in_is_bf16, rows, gamma, beta, out, out_is_bf16, perm, T, Nsp, add, s, out_rs);
-    case 2048: return ln_launch<8>(x, in_is_bf16, rows, gamma, beta, out, out_is_bf16, perm, T, Nsp, add, s, out_rs);
+#define VP_LN(NCH, HALF) \
+  return ln_launch<NCH, HALF>(x, in_is_bf16, rows, gamma, beta, out, out_is_bf16, perm, T, Nsp, add, s, out_rs)
+  switch (D) {  // D = 128 k: k chunks of 128 columns, the odd k with a half last chunk
+    case 128: VP_LN(1, true);
+    case 256: VP_LN(1, false);
+    case 384: VP_LN(2, true);
+    case 512: VP_LN(2, false);
+    case 640: VP_LN(3, true);
+    case 768: VP_LN(3, false);
+    case 896: VP_LN(4, true);
+    case 1024: VP_LN(4, false);
+    case 1152: VP_LN(5, true);
+    case 1280: VP_LN(5, false);
+    case 1408: VP_LN(6, true);
+    case 1536: VP_LN(6, false);
+    case 2048: VP_LN(8, false);
   }
+#undef VP_LN
   return hipErrorInvalidValue;
 }
 

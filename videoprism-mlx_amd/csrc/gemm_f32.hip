@@ -149,8 +149,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
 // sums, 5-9 % faster (q|k|v 818 vs 883 us, post 278 vs 302, ffn2 1057 vs 1151).  The register-staged form
 // measured 0-8 % faster than v1 (profiles/r06/fp32_gemm_ab.txt); a K-tile of 32 (two workgroups per CU) was
 // 8-38 % slower.  Its GELU epilogue is gelu_erfc_fit2 (no libm branches; ffn_layer1 1157 vs 1228 us).
-template <int EPI>
-__global__ __launch_bounds__(256) void gemm_f32_kernel2(const float* __restrict__ A, int64_t lda,
+// TWO (version 3): two accumulator sets, steps 0..3 of every K-tile into the first and 4..7 into the second, added
+// once before the epilogue.  A single chain's rounding error grows as sqrt(K) (rms against fp64 on unit outputs:
+// 6.7e-7 at K = 1408, 1.40e-6 at 6144); two chains of half the length bring it down by about sqrt(2).  Used by
+// the handles whose widths are new with the Giant encoder (vp_internal.h Fwd::f32_two_chains): every other
+// launch keeps the one chain and its sums bitwise.
+template <int EPI, bool TWO = false>
+__global__ __launch_bounds__(256, TWO ? 2 : 1) void gemm_f32_kernel2(const float* __restrict__ A, int64_t lda,
                                                         const float* __restrict__ W, int64_t ldw,
                                                         int M, int N, int K, int ngrp, EpiArgs ep) {
   constexpr int TK2 = 16;
@@ -207,6 +212,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel2(const float* __restrict_
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{};
+  [[maybe_unused]] f32x16 acc2[2][2];
+  if constexpr (TWO) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc2[i][j] = f32x16{};
+  }
   const int nk = K / TK2;
   dma(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -227,9 +239,14 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel2(const float* __restrict_
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-        for (int mb = 0; mb < 2; ++mb)
-          acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[nb][st >> 2][st & 3], av[mb][st >> 2][st & 3],
-                                                             acc[nb][mb], 0, 0, 0);
+        for (int mb = 0; mb < 2; ++mb) {
+          if (TWO && st >= 4)
+            acc2[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[nb][st >> 2][st & 3], av[mb][st >> 2][st & 3],
+                                                                acc2[nb][mb], 0, 0, 0);
+          else
+            acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x2f32(wv[nb][st >> 2][st & 3], av[mb][st >> 2][st & 3],
+                                                               acc[nb][mb], 0, 0, 0);
+        }
     };
     // the second half's reads issued behind the first step's MFMAs, so only 4 reads' latency is exposed
     rd(0);
@@ -263,8 +280,12 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel2(const float* __restrict_
       for (int q = 0; q < 4; ++q) {
         const int c = nb * 8 + 2 * q + half;
         const f32x16& a = acc[nb][mb];
-        *reinterpret_cast<f32x4*>(stg + l32 * 64 + 4 * (c ^ (l32 & 7))) =
-            f32x4{a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
+        f32x4 v4 = f32x4{a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
+        if constexpr (TWO) {  // the two chains meet here
+          const f32x16& a2 = acc2[nb][mb];
+          v4 += f32x4{a2[4 * q], a2[4 * q + 1], a2[4 * q + 2], a2[4 * q + 3]};
+        }
+        *reinterpret_cast<f32x4*>(stg + l32 * 64 + 4 * (c ^ (l32 & 7))) = v4;
       }
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the block is in LDS (a wave-private region)
     __builtin_amdgcn_wave_barrier();
@@ -299,6 +320,10 @@ hipError_t launch(const float* A, int64_t lda, const float* W, int64_t ldw, int 
     VP_NOTE_KERNEL(gemm_f32_kernel<EPI>);
     hipLaunchKernelGGL(gemm_f32_kernel<EPI>, dim3((M / TM) * (N / TN)), dim3(256), 0, s, A, lda, W,
                        ldw, M, N, K, ep);
+  } else if (version == 3) {
+    VP_NOTE_KERNEL((gemm_f32_kernel2<EPI, true>));
+    hipLaunchKernelGGL((gemm_f32_kernel2<EPI, true>), dim3((M / TM) * (N / TN)), dim3(256), 0, s, A, lda, W, ldw, M,
+                       N, K, f32_ngrp(M, N, K), ep);
   } else {
     VP_NOTE_KERNEL(gemm_f32_kernel2<EPI>);
     // 4 workgroups per CU fit (48-59 VGPRs, 32 KiB of LDS); at K >= 2048 (ffn_layer2, A streamed from HBM) 3 run

@@ -69,11 +69,18 @@ int vpi::create_encoder(const vp_config* cfg, int device, const std::string& pre
   *out = nullptr;
   if (cfg->num_heads <= 0 || cfg->model_dim % cfg->num_heads)
     return fail(VP_EINVAL, "model_dim must be divisible by num_heads");
-  if (cfg->model_dim / cfg->num_heads != 64) return fail(VP_ENOTSUP, "dim_per_head must be 64");
-  if (cfg->model_dim % 256 || cfg->mlp_dim % 256)
-    return fail(VP_ENOTSUP, "model_dim and mlp_dim must be multiples of 256");
   if (cfg->fprop_dtype != VP_F32 && cfg->fprop_dtype != VP_BF16)
     return fail(VP_EINVAL, "fprop_dtype must be VP_F32 or VP_BF16");
+  // fp32 runs 64- and 88-wide heads (88: the Giant encoder, 1408 / 16) at any model_dim % 128 == 0; the bf16
+  // attention kernels and 256-wide GEMM tiles are 64-wide heads and model_dim % 256 == 0 only
+  const bool f32 = cfg->fprop_dtype == VP_F32;
+  const int dph = cfg->model_dim / cfg->num_heads;
+  if (!supported_dh(!f32, dph))
+    return fail(VP_ENOTSUP, dph == 88 ? "dim_per_head 88 needs fprop_dtype float32 (bfloat16 runs dim_per_head 64 only)"
+                                      : "dim_per_head must be 64, or 88 with fprop_dtype float32");
+  if (cfg->model_dim % (f32 ? 128 : 256) || cfg->mlp_dim % 256)
+    return fail(VP_ENOTSUP, f32 ? "model_dim must be a multiple of 128 and mlp_dim of 256"
+                                : "model_dim and mlp_dim must be multiples of 256 with fprop_dtype bfloat16");
   if (cfg->patch_size <= 0 || cfg->pos_emb_t <= 0 || cfg->pos_emb_h <= 0 || cfg->pos_emb_w <= 0)
     return fail(VP_EINVAL, "bad patch_size / pos_emb_shape");
   if (cfg->num_spatial_layers < 0 || cfg->num_temporal_layers < 0)
@@ -309,6 +316,7 @@ int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int6
   Fwd f;
   f.s = s; f.bf = bf; f.M = Mp; f.D = D; f.NH = NH; f.cap = c.atten_logit_cap;
   f.hb = hb; f.big = big;
+  f.f32_two_chains = f32_two_chains(c);
   f.st_part = reinterpret_cast<float*>(ws + L.st_part);
   f.ln_rs = reinterpret_cast<float*>(ws + L.ln_rs);
   f.pf = &h->prof;
@@ -502,7 +510,7 @@ int vp_dev_gemm_kernel(int which, int epi, const void* A, const void* W, int64_t
                        int64_t K, void* out, const float* bias, const void* resid, const float* pos,
                        int64_t pos_rows, const float* rowpad, void* stream) {
   using namespace vp;
-  const char* e = which == 1 ? nullptr : (which == 32 || which == 33) ? gemm_f32_check((int)M, (int)N, (int)K, K, K)
+  const char* e = which == 1 ? nullptr : (which >= 32 && which <= 34) ? gemm_f32_check((int)M, (int)N, (int)K, K, K)
                                                                        : gemm_bf16_check((int)M, (int)N, (int)K, K, K);
   if (e) return fail(VP_EINVAL, e);
   const EpiArgs ep = epi_args(out, N, bias, resid, N, pos, pos_rows > 0 ? pos_rows : 1, rowpad);
@@ -515,10 +523,10 @@ int vp_dev_gemm_kernel(int which, int epi, const void* A, const void* W, int64_t
     if (!gemm_bf16_small_ok(epi, (int)M, (int)N, (int)K, K, K))
       return fail(VP_EINVAL, "small-M GEMM: epilogue 0, 1, 2, 4, 5, 7 or 13 and K % 256 == 0");
     VP_HIP(gemm_bf16_small(epi, (const bf16_t*)A, K, (const bf16_t*)W, K, (int)M, (int)N, (int)K, ep, s));
-  } else if (which == 32 || which == 33) {  // fp32: round 1's 16x16x4 kernel (32) / the 32x32x2 kernel (33)
+  } else if (which >= 32 && which <= 34) {  // fp32: round 1's 16x16x4 kernel (32) / the 32x32x2 kernel (33) / with two chains (34)
     VP_HIP(gemm_f32(epi, (const float*)A, K, (const float*)W, K, (int)M, (int)N, (int)K, ep, s, which - 31));
   } else
-    return fail(VP_EINVAL, "which must be 1, 4, 8, 32 or 33");
+    return fail(VP_EINVAL, "which must be 1, 4, 8, 32, 33 or 34");
   return VP_OK;
 }
 
@@ -600,28 +608,57 @@ int vp_dev_ln_stats(int which, const void* src, int64_t M, int64_t D, float* ln_
 
 // Not in the public header: the kernel (vpi::AttnKernel) choose_attention gives a stack of `kind` (vpi::AttnKind;
 // negative: whatever vp_op_attention makes of S and key paddings), or -1 for a bad argument.  No GPU call.
+int vp_dev_attention_choice_dh(int kind, int precision, int64_t S, float cap, int has_key_pad, int64_t dim_per_head);
+
 int vp_dev_attention_choice(int kind, int precision, int64_t S, float cap, int has_key_pad) {
-  if (kind > ATT_TEXT || (precision != VP_F32 && precision != VP_BF16) || S < 1) return -1;
-  if (kind < 0) kind = op_attention_kind(S, has_key_pad != 0);
-  return choose_attention(kind, precision == VP_BF16, S, cap, has_key_pad != 0);
+  return vp_dev_attention_choice_dh(kind, precision, S, cap, has_key_pad, 64);
 }
+
+// ... for heads of dim_per_head values: -2 where no kernel takes that width in that precision (vp_op_attention_dh's
+// VP_ENOTSUP)
+int vp_dev_attention_choice_dh(int kind, int precision, int64_t S, float cap, int has_key_pad, int64_t dim_per_head) {
+  if (kind > ATT_TEXT || (precision != VP_F32 && precision != VP_BF16) || S < 1) return -1;
+  if (!supported_dh(precision == VP_BF16, dim_per_head)) return -2;
+  if (kind < 0) kind = op_attention_kind(S, has_key_pad != 0);
+  return choose_attention(kind, precision == VP_BF16, S, cap, has_key_pad != 0, (int)dim_per_head);
+}
+
+namespace {
+int check_op_dh(int precision, int64_t dim_per_head) {
+  if (supported_dh(precision == VP_BF16, dim_per_head)) return VP_OK;
+  return fail(VP_ENOTSUP, precision == VP_BF16 ? "attention: bfloat16 runs dim_per_head 64 only"
+                                               : "attention: dim_per_head must be 64 or 88");
+}
+}  // namespace
 
 int vp_op_attention(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S,
                     int64_t heads, float cap, const float* key_pad, void* stream) {
+  return vp_op_attention_dh(precision, qkv, o, num_seq, S, heads, 64, cap, key_pad, stream);
+}
+
+int vp_op_attention_dh(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S, int64_t heads,
+                       int64_t dim_per_head, float cap, const float* key_pad, void* stream) {
   if (!qkv || !o || num_seq < 1 || heads < 1) return fail(VP_EINVAL, "bad argument");
   if (precision != VP_F32 && precision != VP_BF16) return fail(VP_EINVAL, "bad precision");
   if (S < 1) return fail(VP_EINVAL, "bad S");
+  if (int rc = check_op_dh(precision, dim_per_head)) return rc;
   VP_HIP(launch_attention(op_attention_kind(S, key_pad != nullptr), precision == VP_BF16, qkv, o, (int)num_seq, (int)S,
-                          (int)heads, cap, key_pad, 0, false, static_cast<hipStream_t>(stream)));
+                          (int)heads, cap, key_pad, 0, false, static_cast<hipStream_t>(stream), (int)dim_per_head));
   return VP_OK;
 }
 
 int vp_op_attention_masked(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S,
                            int64_t heads, float cap, const float* key_pad, int causal, void* stream) {
+  return vp_op_attention_masked_dh(precision, qkv, o, num_seq, S, heads, 64, cap, key_pad, causal, stream);
+}
+
+int vp_op_attention_masked_dh(int precision, const void* qkv, void* o, int64_t num_seq, int64_t S, int64_t heads,
+                              int64_t dim_per_head, float cap, const float* key_pad, int causal, void* stream) {
   if (!qkv || !o || num_seq < 1 || heads < 1 || S < 1) return fail(VP_EINVAL, "bad argument");
   if (precision != VP_F32 && precision != VP_BF16) return fail(VP_EINVAL, "bad precision");
+  if (int rc = check_op_dh(precision, dim_per_head)) return rc;
   VP_HIP(launch_attention(ATT_TEXT, precision == VP_BF16, qkv, o, (int)num_seq, (int)S, (int)heads, cap, key_pad,
-                          causal ? 1 : 0, false, static_cast<hipStream_t>(stream)));
+                          causal ? 1 : 0, false, static_cast<hipStream_t>(stream), (int)dim_per_head));
   return VP_OK;
 }
 
@@ -642,7 +679,7 @@ int vp_op_layernorm(const void* x, int in_dtype, int64_t rows, int64_t D, const 
   if (perm && (T < 1 || Nsp < 1 || rows % (T * Nsp))) return fail(VP_EINVAL, "bad permutation geometry");
   hipError_t e = layernorm(x, in_dtype == VP_BF16, (int)rows, (int)D, gamma, beta, out, out_dtype == VP_BF16,
                            perm, (int)T, (int)Nsp, add, static_cast<hipStream_t>(stream));
-  if (e == hipErrorInvalidValue) return fail(VP_ENOTSUP, "layernorm: D must be 256*k, k in {1..6, 8}");
+  if (e == hipErrorInvalidValue) return fail(VP_ENOTSUP, "layernorm: D must be 128*k, k in {1..12, 16}");
   VP_HIP(e);
   return VP_OK;
 }

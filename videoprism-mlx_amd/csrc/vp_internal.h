@@ -454,15 +454,19 @@ enum AttnKernel {
   ATTN_SEQ = 2,       // attention_seq_bf16: 16 < S <= 256, optionally causal
   ATTN_LONG = 3,      // attention_long_bf16: any S, no masks
   ATTN_MASKED = 4,    // attention_masked: online softmax, any S, cap, masks and dtype
-  ATTN_F32 = 5,       // attention_f32: S <= 256
+  ATTN_F32 = 5,       // attention_f32: S <= 256 (88-wide heads outside the fast cap range: S <= f32_generic_max_s)
   ATTN_F32_MFMA = 6,  // attention_f32_mfma: any S, 0 < cap <= kMaxFastCap
 };
 
 // The one choice of attention kernel: the forward (run_stack) and the op-level entry points (vp_op_attention*,
 // which the kernel parity tests call) all come through here.  Every kernel but ATTN_MASKED and ATTN_F32 has the
 // max-free softmax only, hence fast_cap.  No tier depends on key paddings: ATT_LONG has none by contract and
-// every kernel an ATT_VIDEO / ATT_TEXT stack can get takes them.
-inline AttnKernel choose_attention(int kind, bool bf16, int64_t S, float cap, bool /*has_key_pad*/) {
+// every kernel an ATT_VIDEO / ATT_TEXT stack can get takes them.  dh: head width, 64, or 88 in fp32 (supported_dh);
+// it moves one boundary: attention_f32's generic kernel keeps K|V of a sequence in LDS, which 88-wide heads fill at
+// S = f32_generic_max_s(88) = 224, so without a fast cap (no MFMA kernel from S = 128) longer sequences go to ATTN_MASKED.
+inline bool supported_dh(bool bf16, int64_t dh) { return dh == 64 || (!bf16 && dh == 88); }
+
+inline AttnKernel choose_attention(int kind, bool bf16, int64_t S, float cap, bool /*has_key_pad*/, int dh = 64) {
   const bool fast = fast_cap(cap);
   if (kind == ATT_TEXT) return bf16 && fast && S > 16 && S <= 256 ? ATTN_SEQ : ATTN_MASKED;
   if (bf16 && !fast) return ATTN_MASKED;
@@ -470,30 +474,34 @@ inline AttnKernel choose_attention(int kind, bool bf16, int64_t S, float cap, bo
     if (!bf16) return fast ? ATTN_F32_MFMA : ATTN_MASKED;
     return S >= 256 ? ATTN_LONG : S > 16 ? ATTN_SEQ : ATTN_TEMPORAL;
   }
-  if (!bf16) return S <= 256 ? ATTN_F32 : fast ? ATTN_F32_MFMA : ATTN_MASKED;
+  if (!bf16) {
+    if (S <= 256 && (S <= vp::f32_generic_max_s(dh) || (fast && S >= 128))) return ATTN_F32;
+    return fast ? ATTN_F32_MFMA : ATTN_MASKED;
+  }
   return S == 256 ? ATTN_SPATIAL : S <= 16 ? ATTN_TEMPORAL : S < 256 ? ATTN_SEQ : ATTN_MASKED;
 }
 
 // vp_op_attention has no kind: sequences past 256 keys without paddings are the auxiliary encoder's
 inline int op_attention_kind(int64_t S, bool has_key_pad) { return S > 256 && !has_key_pad ? ATT_LONG : ATT_VIDEO; }
 
-// Launches choose_attention's kernel over qkv [num_seq * S][3 * heads * 64] -> o.  ATT_LONG passes no key
+// Launches choose_attention's kernel over qkv [num_seq * S][3 * heads * dh] -> o.  ATT_LONG passes no key
 // paddings, only ATT_TEXT a causal mask; blk: q|k|v in the row-blocked layout (ATTN_SPATIAL only).
 inline hipError_t launch_attention(int kind, bool bf16, const void* qkv, void* o, int num_seq, int S, int heads, float cap,
-                                   const float* key_pad, int causal, bool blk, hipStream_t s) {
+                                   const float* key_pad, int causal, bool blk, hipStream_t s, int dh = 64) {
   using namespace vp;
+  if (!supported_dh(bf16, dh)) return hipErrorNotSupported;
   if (kind == ATT_LONG) key_pad = nullptr;
   if (kind != ATT_TEXT) causal = 0;
   const bf16_t* qb = static_cast<const bf16_t*>(qkv);
   bf16_t* ob = static_cast<bf16_t*>(o);
-  switch (choose_attention(kind, bf16, S, cap, key_pad != nullptr)) {
+  switch (choose_attention(kind, bf16, S, cap, key_pad != nullptr, dh)) {
     case ATTN_SPATIAL: return attention_spatial_bf16(qb, ob, num_seq, heads, cap, key_pad, s, blk);
     case ATTN_TEMPORAL: return attention_temporal_bf16(qb, ob, num_seq, S, heads, cap, key_pad, s);
     case ATTN_SEQ: return attention_seq_bf16(qb, ob, num_seq, S, heads, cap, key_pad, s, causal);
     case ATTN_LONG: return attention_long_bf16(qb, ob, num_seq, S, heads, cap, s);
-    case ATTN_MASKED: return attention_masked(qkv, o, bf16, num_seq, S, heads, cap, key_pad, causal, s);
-    case ATTN_F32: return attention_f32((const float*)qkv, (float*)o, num_seq, S, heads, cap, key_pad, s);
-    case ATTN_F32_MFMA: return attention_f32_mfma((const float*)qkv, (float*)o, num_seq, S, heads, cap, key_pad, s);
+    case ATTN_MASKED: return attention_masked(qkv, o, bf16, num_seq, S, heads, cap, key_pad, causal, s, dh);
+    case ATTN_F32: return attention_f32((const float*)qkv, (float*)o, num_seq, S, heads, cap, key_pad, s, dh);
+    case ATTN_F32_MFMA: return attention_f32_mfma((const float*)qkv, (float*)o, num_seq, S, heads, cap, key_pad, s, dh);
   }
   return hipErrorInvalidValue;
 }
@@ -504,6 +512,15 @@ inline void set_tattn_cap(vp::EpiArgs& ep, float cap, int heads) {
   ep.cap = cap; ep.heads = heads;
   ep.cap_c1 = 2.0f * 1.4426950408889634f / cap;
   ep.cap_c2 = cap * 1.4426950408889634f;
+}
+
+// The fp32 GEMM sums each output in one k-ordered chain, whose rounding error grows as sqrt(K): at Base's and
+// Large's widths (K <= 4096) the forward stays at 6e-6 - 7e-6 of the fp64 oracle, at Giant's (K = 1408 and 6144
+// in every layer) it reaches the project's 1e-5 bar.  Configurations that are new with Giant -- 88-wide heads, or a
+// model_dim that is no multiple of 256 -- run the two-chain kernel (gemm_f32 version 3); every configuration the
+// library took before keeps its sums bitwise.
+inline bool f32_two_chains(const vp_config& c) {
+  return c.fprop_dtype == VP_F32 && (c.model_dim / c.num_heads != 64 || c.model_dim % 256 != 0);
 }
 
 // One forward pass's launch context: stream, dtype, row count, scratch buffers and the profiler.
@@ -531,6 +548,7 @@ struct Fwd {
   int causal = 1;            // ATT_TEXT: merged causal + padding mask (enable_causal_atten)
   bool xs_f32 = false;       // bf16 GEMMs over an fp32 residual stream (text tower; no folding)
   bool small_m = false;      // few rows (text tower): 64 x 64-tile GEMM, K split over the waves (gemm_bf16_small.hip)
+  bool f32_two_chains = false;  // fp32 GEMMs with two accumulation chains per output (f32_two_chains(cfg))
   void* hb = nullptr;        // [M][D] LayerNorm / attention output
   void* big = nullptr;       // [M][max(3D, F)] q|k|v, FFN hidden
   float* st_part = nullptr;  // [D/128][M][2] partial row statistics (folded LayerNorm)
@@ -570,7 +588,7 @@ struct Fwd {
       return vp::gemm_bf16_small(epi, (const vp::bf16_t*)A, K, (const vp::bf16_t*)Wt, K, M, N, K, ep, s);
     }
     if (bf) return vp::gemm_bf16_auto(epi, (const vp::bf16_t*)A, K, (const vp::bf16_t*)Wt, K, M, N, K, ep, s);
-    return vp::gemm_f32(epi, (const float*)A, K, (const float*)Wt, K, M, N, K, ep, s);
+    return vp::gemm_f32(epi, (const float*)A, K, (const float*)Wt, K, M, N, K, ep, s, f32_two_chains ? 3 : 2);
   }
 
   // (rstd, -mean*rstd) of the residual stream from the producers' partial statistics
@@ -631,7 +649,7 @@ struct Fwd {
           return gemm(EPI_BF16, hb, D, lw.wqkv, 3 * D, big, 3 * D, lw.bqkv, nullptr, nullptr, 1, nullptr); }));
       }
       if (!tattn) VP_HIP(rec(acls, aflops, abytes, [&] {
-        return launch_attention(kind, bf, big, hb, num_seq, S, NH, cap, pad, causal, sblk, s); }));
+        return launch_attention(kind, bf, big, hb, num_seq, S, NH, cap, pad, causal, sblk, s, D / NH); }));
       VP_HIP(rec(PC_GEMM_POST, 2.0 * dM * dD * dD, gbytes(dD, dD, dE, dE), [&] {
         return gemm(fold ? EPI_RESID_BF16_ST : epi_resid, hb, D, lw.wpost, D, xs, D, lw.bpost, xs, nullptr, 1,
                     nullptr); }));

@@ -123,13 +123,14 @@ hipError_t gemm_bf16_auto(int epi, const bf16_t* A, int64_t lda, const bf16_t* W
 
 // ---- fp32 GEMM for fprop_dtype=float32 (gemm_f32.hip) ----
 const char* gemm_f32_check(int M, int N, int K, int64_t lda, int64_t ldw);
-// version 2 (default): the 32x32x2 kernel; 1: round 1's 16x16x4 kernel (A/B through vp_dev_gemm_kernel)
+// version 2 (default): the 32x32x2 kernel; 1: round 1's 16x16x4 kernel (A/B through vp_dev_gemm_kernel); 3: the
+// 32x32x2 kernel with two accumulation chains per output (half the chain, about 1 / sqrt(2) the rounding error)
 hipError_t gemm_f32(int epi, const float* A, int64_t lda, const float* W, int64_t ldw, int M,
                     int N, int K, const EpiArgs& ep, hipStream_t s, int version = 2);
 
 // ---- attention (attention.hip) ----
 // qkv: rows of [q(D) | k(D) | v(D)], row r = seq * S + s; q pre-scaled by dh^-0.5.
-// o: rows of D = heads*64.  key_pad: optional [num_seq * S] (1 = padded key).
+// o: rows of D = heads*dh (dh = 64 unless a launcher takes it).  key_pad: optional [num_seq * S] (1 = padded key).
 // blk: qkv in the row-blocked layout of EPI_BF16_LN_BLK ([M/16][3D/32][16][32])
 hipError_t attention_spatial_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int heads,
                                   float cap, const float* key_pad, hipStream_t s, bool blk = false);
@@ -139,14 +140,20 @@ hipError_t attention_seq_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S, 
                               const float* key_pad, hipStream_t s, int causal = 0);
 hipError_t attention_temporal_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S, int heads,
                                    float cap, const float* key_pad, hipStream_t s);
+// The fp32 kernels below and attention_masked's fp32 instantiation take heads of dh = 64 or 88 floats (88: the
+// Giant encoder, 1408 / 16); qkv rows are then [q|k|v] of D = heads * dh each and o rows of D.  The bf16
+// kernels are dh = 64 only.
+// longest sequence of attention_f32's generic kernel: K|V of one (sequence, head) in LDS, 8 S dh bytes of 160 KiB
+constexpr int f32_generic_max_s(int dh) { return dh <= 64 ? 256 : 224; }
 // fp32, S <= 256: S >= 128 with 0 < cap <= 50 on the MFMA (attention_f32_mfma), else the generic kernel
+// (S <= f32_generic_max_s(dh))
 hipError_t attention_f32(const float* qkv, float* o, int num_seq, int S, int heads, float cap,
-                         const float* key_pad, hipStream_t s);
+                         const float* key_pad, hipStream_t s, int dh = 64);
 // fp32 on v_mfma_f32_32x32x2f32, any S, no causal mask: hipErrorNotSupported unless 0 < cap <= 50 (the
 // max-free softmax), which is when the host chooses it (vp_internal.h choose_attention); attention_f32 then
 // takes its generic kernel
 hipError_t attention_f32_mfma(const float* qkv, float* o, int num_seq, int S, int heads, float cap,
-                              const float* key_pad, hipStream_t s);
+                              const float* key_pad, hipStream_t s, int dh = 64);
 
 // ---- elementwise / normalisation (elementwise.hip) ----
 enum RowPerm { PERM_NONE = 0, PERM_BTN_TO_BNT = 1, PERM_BNT_TO_BTN = 2 };
@@ -154,7 +161,7 @@ enum RowPerm { PERM_NONE = 0, PERM_BTN_TO_BNT = 1, PERM_BNT_TO_BTN = 2 };
 // (bf16 or f32), zero-padded K.
 hipError_t patchify(const void* video, int in_dtype, void* patches, int out_is_bf16, int BT,
                     int H, int W, int C, int P, int kpad, hipStream_t s);
-// LayerNorm over D of fp32 or bf16 rows; gamma already holds (1 + scale).  Output row r goes
+// LayerNorm over D = 128 k (k in 1..12 or 16) of fp32 or bf16 rows; gamma already holds (1 + scale).  Output row r goes
 // to row perm(r); `add` (optional, fp32 [add_rows][D]) is added by the *output* row's t index.
 // out_rs (optional): (rstd, -mean*rstd) of each stored output row (as ln_rs above), by
 // output row index
@@ -180,10 +187,10 @@ hipError_t ln_row_stats(const bf16_t* x, int64_t M, int D, float* ln_rs, hipStre
 // auxiliary-encoder self-attention over S = T*N tokens (S % 256 == 0), capped, no masks
 hipError_t attention_long_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S, int heads, float cap,
                                hipStream_t s);
-// generic fp32-math attention (any S, dh 64) with key paddings and the causal merge of
-// layers.py:111-179; qkv / o in bf16 (in_is_bf16) or fp32
+// generic fp32-math attention (any S) with key paddings and the causal merge of layers.py:111-179; qkv / o in
+// bf16 (in_is_bf16, dh 64) or fp32 (dh 64 or 88)
 hipError_t attention_masked(const void* qkv, void* o, int in_is_bf16, int num_seq, int S, int heads,
-                            float cap, const float* key_pad, int causal, hipStream_t s);
+                            float cap, const float* key_pad, int causal, hipStream_t s, int dh = 64);
 // contrastive pooler: logits[g][h][s] = x[g*S+s] . U[h]; then softmax per (g,h) and
 // z[g][h][:] = sum_s p x (zpart scratch: [G][pool_chunks(S)][H][D], stats [G*H][2])
 // (bf16 x with Ut = [32][D] bf16 (U_hi | U_lo | 0) and S % 32 == 0: MFMA kernel)

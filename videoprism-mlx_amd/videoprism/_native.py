@@ -96,6 +96,8 @@ _SIGNATURES = {
                            c_int64, c_void_p, c_void_p]),
     "vp_op_attention": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float,
                                 c_void_p, c_void_p]),
+    "vp_op_attention_dh": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_float,
+                                   c_void_p, c_void_p]),
     "vp_op_layernorm": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                 c_int, c_int, c_int64, c_int64, c_void_p, c_void_p]),
     "vp_op_patchify": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64,
@@ -105,6 +107,8 @@ _SIGNATURES = {
     "vp_op_pool_l2": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "vp_op_attention_masked": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float,
                                        c_void_p, c_int, c_void_p]),
+    "vp_op_attention_masked_dh": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_float,
+                                          c_void_p, c_int, c_void_p]),
     "vp_op_similarity": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     # LvT video-text model (FactorizedVideoCLIP)
     "vp_clip_create": (c_int, [POINTER(vp_clip_config), c_int, POINTER(c_void_p)]),
@@ -150,6 +154,7 @@ _SIGNATURES = {
                                   c_void_p, c_void_p, c_int64, c_float, c_void_p]),
     # which attention kernel the library picks (vpi::choose_attention); no GPU call
     "vp_dev_attention_choice": (c_int, [c_int, c_int, c_int64, c_float, c_int]),
+    "vp_dev_attention_choice_dh": (c_int, [c_int, c_int, c_int64, c_float, c_int, c_int64]),
     # the pooler, small GEMM and text kernels one at a time (tests/test_gpu_clip_kernels.py)
     "vp_dev_pool_split_u": (c_int, [c_void_p, c_int64, c_int64, c_void_p]),
     "vp_dev_pool_chunks": (c_int, [c_int64]),
@@ -461,32 +466,35 @@ ATT_OP, ATT_VIDEO, ATT_LONG, ATT_TEXT = -1, 0, 1, 2
 ATTN_KERNELS = ("SPATIAL", "TEMPORAL", "SEQ", "LONG", "MASKED", "F32", "F32_MFMA")
 
 
-def dev_attention_choice(kind, precision, S, cap, has_key_pad=False) -> str:
-    """Name of the attention kernel a stack of `kind` gets (no GPU call, no device needed)."""
-    k = load().vp_dev_attention_choice(kind, precision, S, float(cap), 1 if has_key_pad else 0)
+def dev_attention_choice(kind, precision, S, cap, has_key_pad=False, dim_per_head=64) -> str:
+    """Name of the attention kernel a stack of `kind` with heads of dim_per_head values gets (no GPU call, no
+    device needed); NotImplementedError where the library has no kernel of that width in that precision."""
+    k = load().vp_dev_attention_choice_dh(kind, precision, S, float(cap), 1 if has_key_pad else 0, dim_per_head)
+    if k == -2:
+        raise NotImplementedError(f"no attention kernel for dim_per_head {dim_per_head} in precision {precision}")
     if k < 0:
         raise ValueError(f"bad argument: kind {kind}, precision {precision}, S {S}")
     return ATTN_KERNELS[k]
 
 
-def op_attention(qkv, num_seq, S, heads, cap, key_pad=None, out=None, stream=None):
+def op_attention(qkv, num_seq, S, heads, cap, key_pad=None, out=None, stream=None, dim_per_head=64):
     import torch
-    D = heads * 64
+    D = heads * dim_per_head
     if out is None:
         out = torch.empty((num_seq * S, D), dtype=qkv.dtype, device=qkv.device)
-    call("vp_op_attention", _prec(qkv), _ptr(qkv), _ptr(out), num_seq, S, heads, float(cap),
+    call("vp_op_attention_dh", _prec(qkv), _ptr(qkv), _ptr(out), num_seq, S, heads, dim_per_head, float(cap),
          _ptr(key_pad), _stream(stream))
     return out
 
 
 def op_attention_masked(qkv, num_seq, S, heads, cap, key_pad=None, causal=False, out=None,
-                        stream=None):
+                        stream=None, dim_per_head=64):
     """Generic fp32-math attention with key paddings and the causal merge (text tower)."""
     import torch
-    D = heads * 64
+    D = heads * dim_per_head
     if out is None:
         out = torch.empty((num_seq * S, D), dtype=qkv.dtype, device=qkv.device)
-    call("vp_op_attention_masked", _prec(qkv), _ptr(qkv), _ptr(out), num_seq, S, heads, float(cap),
+    call("vp_op_attention_masked_dh", _prec(qkv), _ptr(qkv), _ptr(out), num_seq, S, heads, dim_per_head, float(cap),
          _ptr(key_pad), 1 if causal else 0, _stream(stream))
     return out
 
