@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define VP_ABI_VERSION 7
+#define VP_ABI_VERSION 8
 
 typedef struct vp_handle vp_handle;
 
@@ -228,7 +228,9 @@ int vp_op_similarity(const float* video_emb, const float* text_emb, int64_t B, i
  * frame_paddings) (models.py:116-212, 268-303).  Parameters are the Flax leaves under 'params':
  * 'vision_encoder/...' (the FactorizedEncoder leaves above), 'auxiliary_encoder/...',
  * 'contrastive_vision_pooler/...', 'text_encoder/...' (88 leaves for a scanned model,
- * encoders_test.py:339).  Same conventions as vp_handle (borrowed device pointers, async on
+ * encoders_test.py:339; 92 with norm_policy 1).  model_dim: a multiple of 128 up to 1536 (the pooler
+ * kernels' range, VP_ENOTSUP past it), so videoprism_lvt_v1_giant (1408) runs with VP_F32; with VP_BF16 Giant's
+ * widths get vp_create's dim_per_head refusal.  Same conventions as vp_handle (borrowed device pointers, async on
  * `stream`, no allocation in the encode calls, one device per handle, not thread-safe). */
 typedef struct vp_clip vp_clip;
 
@@ -238,6 +240,11 @@ typedef struct vp_clip_config {
   int32_t vocabulary_size;       /* 32000 (c4_en, models.py:55-60) */
   int32_t num_unimodal_layers;   /* 12: text tower depth */
   int32_t enable_causal_atten;   /* 1 */
+  int32_t norm_policy;           /* text tower only (encoders.py:899; the vision and auxiliary stacks are always
+                                  * 'pre'): 0 'pre', 1 'primer_hybrid' (videoprism_lvt_v1_giant: a LayerNorm before
+                                  * and after each sublayer, layers.py:388-430, :819-860; the scanned text stack
+                                  * then has 20 leaves, pre_layer_norm / post_layer_norm in place of layer_norm);
+                                  * any other value: VP_ENOTSUP */
 } vp_clip_config;
 
 int vp_clip_create(const vp_clip_config* cfg, int device, vp_clip** out);

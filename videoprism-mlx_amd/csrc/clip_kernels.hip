@@ -16,6 +16,10 @@
 //   pool_reduce : z[g][h][:] = sum_c zpart
 //   small_gemm  : out[m][n] = A[m][:] . Wt[:][n] + bias[n], batched (enc per head, then post)
 //   ln_l2_rows  : LayerNorm (layers.py:208-270) and/or _l2_normalize (encoders.py:50-67), fp32
+// Widths: D up to kPoolMaxD = 1536 (LayerNorm's range; Giant is 1408 = 22 x 64 = 5 x 256 + 128).  pool_logits takes
+// D = 64 k, with U for all heads in LDS (more than 64 KB past D = 1024 at 16 heads: the launcher opts in);
+// pool_wsum takes D = 128 k, the odd k with a 128-wide last column block; ln_l2_rows any D up to the limit.  Every
+// width up to 1024 runs the instantiation, grid and summation order it always ran.
 // Text tower: text_embed = Embedding(ids)*sqrt(D) + sinusoidal PositionalEmbedding, with the
 // CLS token appended (encoders.py:190-266, :700-740).  similarity = video_emb . text_emb^T.
 #include "vp_common.h"
@@ -62,6 +66,10 @@ __device__ __forceinline__ float block_max(float v, float* red) {
 
 constexpr int kPlRows = 64;  // rows per workgroup (16 per wave)
 
+// NJ: 64-column steps a lane keeps in registers: 16 (D <= 1024, the kernel every width up to Large runs) or 24
+// (D <= 1536; 22 steps at Giant's 1408).  U [H][D] sits in dynamic LDS whole: past 64 KB (16 heads x 1408 columns
+// are 90,112 B) the launcher opts in to the larger allocation, as the 88-wide fp32 attention kernel does.
+template <int NJ>
 __global__ __launch_bounds__(256) void pool_logits_kernel(const void* __restrict__ x, int in_bf16, int64_t rows,
                                                           int S, int D, const float* __restrict__ U, int H,
                                                           float* __restrict__ logits) {
@@ -74,14 +82,14 @@ __global__ __launch_bounds__(256) void pool_logits_kernel(const void* __restrict
   for (int rr = 0; rr < kPlRows / 4; ++rr) {
     const int64_t r = (int64_t)blockIdx.x * kPlRows + w * (kPlRows / 4) + rr;
     if (r >= rows) break;  // uniform per wave
-    float xv[16];
+    float xv[NJ];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) xv[j] = j < nj ? ldx(x, in_bf16, r * D + lane + 64 * j) : 0.0f;
+    for (int j = 0; j < NJ; ++j) xv[j] = j < nj ? ldx(x, in_bf16, r * D + lane + 64 * j) : 0.0f;
     const int64_t g = r / S, s = r % S;
     for (int h = 0; h < H; ++h) {
       float a = 0.0f;
 #pragma unroll
-      for (int j = 0; j < 16; ++j)
+      for (int j = 0; j < NJ; ++j)
         if (j < nj) a = fmaf(xv[j], Us[h * D + lane + 64 * j], a);
       a = wave_sum(a);
       if (lane == 0) logits[(g * H + h) * S + s] = a;
@@ -149,15 +157,17 @@ constexpr int kPwRows = 256;  // rows per chunk
 constexpr int kPwMaxH = 16;
 
 // zpart[g][c][h][d] = sum over rows of chunk c of p[g,h,s] x[g*S+s][d]: a workgroup owns one
-// (g, 256-row chunk, 256-column quarter) with 128 threads; a thread owns two adjacent columns (one 4-byte
+// (g, 256-row chunk, 256-column block) with 128 threads; a thread owns two adjacent columns (one 4-byte
 // bf16 pair / 8-byte fp32 pair per row) and all 16 head sums of each, the probabilities of the chunk sit in
-// LDS (float4 broadcast reads).  Each column is summed over the rows in row order.
+// LDS (float4 broadcast reads).  Each column is summed over the rows in row order.  D = 128 k with k odd
+// (1408 = 5 x 256 + 128): the last column block is 128 wide, its second wave fills its share of the
+// probabilities and leaves, so no lane reads or writes a column past D and x is still read once.
 __global__ __launch_bounds__(128) void pool_wsum_kernel(const void* __restrict__ x, int in_bf16, int S, int D,
                                                         int H, const float* __restrict__ logits,
                                                         const float* __restrict__ stats, int C,
                                                         float* __restrict__ zpart) {
   __shared__ __attribute__((aligned(16))) float ps[kPwRows][kPwMaxH];
-  const int nq = D >> 8;
+  const int nq = (D + 255) >> 8;
   const int q = blockIdx.x % nq;
   const int gc = blockIdx.x / nq;
   const int g = gc / C;
@@ -175,6 +185,7 @@ __global__ __launch_bounds__(128) void pool_wsum_kernel(const void* __restrict__
   }
   __syncthreads();
   const int d = q * 256 + 2 * threadIdx.x;
+  if (d >= D) return;  // the half block's second wave, whole
   float acc0[kPwMaxH], acc1[kPwMaxH];
 #pragma unroll
   for (int h = 0; h < kPwMaxH; ++h) acc0[h] = acc1[h] = 0.0f;
@@ -303,34 +314,36 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   out[m * ldo + n] = v + (bias ? bias[n] : 0.0f);
 }
 
+// NV: 256-column steps a thread keeps in registers: 4 (D <= 1024) or 6 (D <= 1536)
+template <int NV>
 __global__ __launch_bounds__(256) void ln_l2_rows_kernel(const void* __restrict__ x, int in_bf16, int64_t stride,
                                                          int D, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, int do_l2,
                                                          float* __restrict__ out) {
   __shared__ float red[4];
   const int64_t r = blockIdx.x;
-  float v[4];
+  float v[NV];
   const int nj = (D + 255) >> 8;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < NV; ++j) {
     const int d = threadIdx.x + 256 * j;
     v[j] = (j < nj && d < D) ? ldx(x, in_bf16, r * stride + d) : 0.0f;
   }
   if (gamma) {
     float s = 0.0f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) s += v[j];
+    for (int j = 0; j < NV; ++j) s += v[j];
     const float mean = block_sum(s, red) / (float)D;
     float q = 0.0f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < NV; ++j) {
       const int d = threadIdx.x + 256 * j;
       const float c = (j < nj && d < D) ? v[j] - mean : 0.0f;
       q = fmaf(c, c, q);
     }
     const float rstd = rsqrtf(block_sum(q, red) / (float)D + 1e-6f);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < NV; ++j) {
       const int d = threadIdx.x + 256 * j;
       if (j < nj && d < D) v[j] = (v[j] - mean) * rstd * gamma[d] + beta[d];
       else v[j] = 0.0f;
@@ -339,13 +352,13 @@ __global__ __launch_bounds__(256) void ln_l2_rows_kernel(const void* __restrict_
   if (do_l2) {
     float q = 0.0f;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) q = fmaf(v[j], v[j], q);
+    for (int j = 0; j < NV; ++j) q = fmaf(v[j], v[j], q);
     const float inv = 1.0f / sqrtf(block_sum(q, red) + 1e-12f);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] *= inv;
+    for (int j = 0; j < NV; ++j) v[j] *= inv;
   }
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < NV; ++j) {
     const int d = threadIdx.x + 256 * j;
     if (j < nj && d < D) out[r * D + d] = v[j];
   }
@@ -388,7 +401,7 @@ __global__ __launch_bounds__(256) void similarity_kernel(const float* __restrict
 
 hipError_t pool_logits(const void* x, int in_bf16, int64_t rows, int S, int D, const float* U, const bf16_t* Ut,
                        int H, float* logits, hipStream_t s) {
-  if (D % 64 || D > 1024 || H < 1 || H > kPwMaxH || rows % S) return hipErrorInvalidValue;
+  if (D % 64 || D > kPoolMaxD || H < 1 || H > kPwMaxH || rows % S) return hipErrorInvalidValue;
   if (in_bf16 && Ut && S % 32 == 0) {
     const int64_t grid = (rows / 32 + 3) / 4;
     hipLaunchKernelGGL(pool_logits_mfma_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)x, rows, S,
@@ -396,19 +409,29 @@ hipError_t pool_logits(const void* x, int in_bf16, int64_t rows, int S, int D, c
     return hipGetLastError();
   }
   const int64_t grid = (rows + kPlRows - 1) / kPlRows;
-  hipLaunchKernelGGL(pool_logits_kernel, dim3((unsigned)grid), dim3(256), (size_t)H * D * 4, s, x, in_bf16, rows,
-                     S, D, U, H, logits);
+  const size_t lds = (size_t)H * D * 4;
+  if (D <= 1024) {
+    hipLaunchKernelGGL(pool_logits_kernel<16>, dim3((unsigned)grid), dim3(256), lds, s, x, in_bf16, rows, S, D, U, H,
+                       logits);
+    return hipGetLastError();
+  }
+  if (lds > 65536) {  // up to 16 x 1536 x 4 = 98,304 B of the CU's 160 KB
+    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&pool_logits_kernel<24>), kPwMaxH * kPoolMaxD * 4);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(pool_logits_kernel<24>, dim3((unsigned)grid), dim3(256), lds, s, x, in_bf16, rows, S, D, U, H,
+                     logits);
   return hipGetLastError();
 }
 
 hipError_t pool_softmax_wsum(const void* x, int in_bf16, int G, int S, int D, int H, const float* logits,
                              float* stats, float* zpart, float* z, hipStream_t s) {
-  if (D % 256 || D > 1024 || H < 1 || H > kPwMaxH) return hipErrorInvalidValue;
+  if (D % 128 || D > kPoolMaxD || H < 1 || H > kPwMaxH) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pool_stats_kernel, dim3(G * H), dim3(256), 0, s, logits, S, stats);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const int C = (S + kPwRows - 1) / kPwRows;
-  hipLaunchKernelGGL(pool_wsum_kernel, dim3(G * C * (D / 256)), dim3(128), 0, s, x, in_bf16, S, D, H, logits, stats,
+  hipLaunchKernelGGL(pool_wsum_kernel, dim3(G * C * ((D + 255) / 256)), dim3(128), 0, s, x, in_bf16, S, D, H, logits, stats,
                      C, zpart);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -447,8 +470,13 @@ hipError_t small_gemm_splitk(const float* A, int64_t lda, const float* Wt, const
 
 hipError_t ln_l2_rows(const void* x, int in_bf16, int64_t stride, int rows, int D, const float* gamma,
                       const float* beta, int do_l2, float* out, hipStream_t s) {
-  if (D < 1 || D > 1024 || rows < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(ln_l2_rows_kernel, dim3(rows), dim3(256), 0, s, x, in_bf16, stride, D, gamma, beta, do_l2, out);
+  if (D < 1 || D > kPoolMaxD || rows < 1) return hipErrorInvalidValue;
+  if (D <= 1024)
+    hipLaunchKernelGGL(ln_l2_rows_kernel<4>, dim3(rows), dim3(256), 0, s, x, in_bf16, stride, D, gamma, beta, do_l2,
+                       out);
+  else
+    hipLaunchKernelGGL(ln_l2_rows_kernel<6>, dim3(rows), dim3(256), 0, s, x, in_bf16, stride, D, gamma, beta, do_l2,
+                       out);
   return hipGetLastError();
 }
 

@@ -269,6 +269,100 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const void* __restrict__
   }
 }
 
+// ---- LayerNorm, then the residual (norm_policy 'primer_hybrid', layers.py:409-425, :846-855) ----
+// xs[r] += LN(y[r] * (1 - pad[r])) in place on the fp32 residual stream.  The padding multiply comes before the
+// LayerNorm, as in the reference, so a padded row is LN(0) = beta and gets xs + beta.  Same layout and two-pass
+// statistics as layernorm_kernel (a wave owns 2 rows, NCH chunks of 4 values per lane, HALF: D = NCH * 256 - 128).
+template <int NCH, bool Y_BF16, bool HALF>
+__global__ __launch_bounds__(256) void layernorm_residual_kernel(const void* __restrict__ y, int rows,
+                                                                 const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta,
+                                                                 const float* __restrict__ pad,
+                                                                 float* __restrict__ xs) {
+  constexpr int D = NCH * 256 - (HALF ? 128 : 0);
+  constexpr int RPW = 2;
+  const int lane = threadIdx.x & 63;
+  const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
+  if (row0 >= rows) return;
+  [[maybe_unused]] const bool dead = HALF && lane >= 32;  // this lane's last chunk lies past the row
+  float4 v[RPW][NCH];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const int row = row0 + r < rows ? row0 + r : rows - 1;  // tail row: recomputed, not stored
+    const float keep = pad ? 1.0f - pad[row] : 1.0f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if constexpr (HALF) {
+        if (c == NCH - 1 && dead) {
+          v[r][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+          continue;
+        }
+      }
+      float4 t;
+      if constexpr (Y_BF16) {
+        const uint2 u = *reinterpret_cast<const uint2*>(static_cast<const bf16_t*>(y) + (int64_t)row * D + c * 256 +
+                                                        lane * 4);
+        t = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                        __uint_as_float(u.y & 0xffff0000u));
+      } else {
+        t = *reinterpret_cast<const float4*>(static_cast<const float*>(y) + (int64_t)row * D + c * 256 + lane * 4);
+      }
+      v[r][c] = make_float4(t.x * keep, t.y * keep, t.z * keep, t.w * keep);
+    }
+  }
+  float s[RPW];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    s[r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) s[r] += (v[r][c].x + v[r][c].y) + (v[r][c].z + v[r][c].w);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) s[r] += __shfl_xor(s[r], off);
+  float ss[RPW];
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const float mean = s[r] * (1.0f / D);
+    ss[r] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      v[r][c].x -= mean; v[r][c].y -= mean; v[r][c].z -= mean; v[r][c].w -= mean;
+      if constexpr (HALF) {
+        if (c == NCH - 1 && dead) v[r][c] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      ss[r] += (v[r][c].x * v[r][c].x + v[r][c].y * v[r][c].y) + (v[r][c].z * v[r][c].z + v[r][c].w * v[r][c].w);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1)
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) ss[r] += __shfl_xor(ss[r], off);
+#pragma unroll
+  for (int r = 0; r < RPW; ++r) {
+    const int row = row0 + r;
+    if (row >= rows) break;
+    const float rstd = 1.0f / sqrtf(ss[r] * (1.0f / D) + 1e-6f);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if constexpr (HALF) {
+        if (c == NCH - 1 && dead) continue;
+      }
+      const int col = c * 256 + lane * 4;
+      const float4 gm = *reinterpret_cast<const float4*>(gamma + col);
+      const float4 bt = *reinterpret_cast<const float4*>(beta + col);
+      float4* xp = reinterpret_cast<float4*>(xs + (int64_t)row * D + col);
+      float4 x = *xp;
+      x.x += v[r][c].x * rstd * gm.x + bt.x;
+      x.y += v[r][c].y * rstd * gm.y + bt.y;
+      x.z += v[r][c].z * rstd * gm.z + bt.z;
+      x.w += v[r][c].w * rstd * gm.w + bt.w;
+      *xp = x;
+    }
+  }
+}
+
 // ---- LayerNorm statistics for the GEMM-folded LayerNorm (EPI_*_LN) ----
 // partials: st[p][row] = (sum, M2) over columns [128p, 128p+128) of the stored bf16 row
 // (vp_common.h ln_combine).  PP: the partial count as a compile-time constant (D = 768: 6, 1024: 8),
@@ -514,6 +608,39 @@ hipError_t layernorm(const void* x, int in_is_bf16, int rows, int D, const float
     case 2048: VP_LN(8, false);
   }
 #undef VP_LN
+  return hipErrorInvalidValue;
+}
+
+hipError_t layernorm_residual(const void* y, int y_is_bf16, int rows, int D, const float* gamma, const float* beta,
+                              const float* pad, float* xs, hipStream_t s) {
+  if (rows < 1) return hipErrorInvalidValue;
+  const dim3 grid((rows + 7) / 8);  // 4 waves x 2 rows
+#define VP_LNR(NCH, HALF)                                                                                            \
+  {                                                                                                                  \
+    if (y_is_bf16)                                                                                                   \
+      hipLaunchKernelGGL((layernorm_residual_kernel<NCH, true, HALF>), grid, dim3(256), 0, s, y, rows, gamma, beta,  \
+                         pad, xs);                                                                                   \
+    else                                                                                                             \
+      hipLaunchKernelGGL((layernorm_residual_kernel<NCH, false, HALF>), grid, dim3(256), 0, s, y, rows, gamma, beta, \
+                         pad, xs);                                                                                   \
+    return hipGetLastError();                                                                                        \
+  }
+  switch (D) {  // layernorm's widths
+    case 128: VP_LNR(1, true);
+    case 256: VP_LNR(1, false);
+    case 384: VP_LNR(2, true);
+    case 512: VP_LNR(2, false);
+    case 640: VP_LNR(3, true);
+    case 768: VP_LNR(3, false);
+    case 896: VP_LNR(4, true);
+    case 1024: VP_LNR(4, false);
+    case 1152: VP_LNR(5, true);
+    case 1280: VP_LNR(5, false);
+    case 1408: VP_LNR(6, true);
+    case 1536: VP_LNR(6, false);
+    case 2048: VP_LNR(8, false);
+  }
+#undef VP_LNR
   return hipErrorInvalidValue;
 }
 

@@ -6,12 +6,21 @@
 //          projection, clip_kernels.hip) -> LayerNorm -> L2 normalise
 //   text:  token embedding * sqrt(D) + sinusoidal positions, CLS appended -> 12 causal pre-LN
 //          ReLU layers (attention_masked) -> unimodal_ln on the CLS row -> L2 normalise
+//          (norm_policy 1, Giant: 16 'primer_hybrid' layers, a LayerNorm before and after each sublayer)
 #include "vp_internal.h"
 
 using namespace vpi;
 
 namespace {
 constexpr int kMaxTextLen = 1024;  // L + 1 (CLS) tokens; TEXT_MAX_LEN is 64 (models.py:53)
+
+// what the pooler kernels take (clip_kernels.hip): whole 128-column blocks up to vp::kPoolMaxD, at most 16 heads
+int check_pooler_dims(const vp_config& v) {
+  if (v.num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
+  if (v.model_dim % 128 || v.model_dim > vp::kPoolMaxD)
+    return fail(VP_ENOTSUP, "pooler kernels need model_dim % 128 == 0, at most " + std::to_string(vp::kPoolMaxD));
+  return VP_OK;
+}
 }
 
 // AttenTokenPoolingLayer weights, packed (see pack_pooler): U [H][D] (query folded into the key
@@ -187,7 +196,8 @@ void build_clip_expected(vp_clip& c) {
   add_pooler_expected(c, "contrastive_vision_pooler/", D, NH, c.pool_dp);
   c.expect("text_encoder/token_emb/emb_var", {(int64_t)cc.vocabulary_size, D});
   c.expect("text_encoder/cls_emb", {1, 1, D});
-  add_stack_expected(c, "text_encoder/unimodal_transformer/x_layers/", cc.num_unimodal_layers, D, 4 * D, NH);
+  add_stack_expected(c, "text_encoder/unimodal_transformer/x_layers/", cc.num_unimodal_layers, D, 4 * D, NH,
+                     cc.norm_policy == 1);
   c.expect("text_encoder/unimodal_ln/scale", {D});
   c.expect("text_encoder/unimodal_ln/bias", {D});
 }
@@ -345,7 +355,7 @@ int pack_text(vp_clip* c) {
     return rc;
   const int NH = c->cfg.video.num_heads;
   return pack_stack(*c, c->bf16(), "text_encoder/unimodal_transformer/x_layers/", c->cfg.num_unimodal_layers, D, 4 * D, NH,
-                    false, c->text);
+                    false, c->text, QKV_PLAIN, c->cfg.norm_policy == 1);
 }
 
 }  // namespace
@@ -358,10 +368,13 @@ int vp_clip_create(const vp_clip_config* cfg, int device, vp_clip** out) {
   if (cfg->num_auxiliary_layers < 0 || cfg->num_unimodal_layers < 0 || cfg->vocabulary_size < 1)
     return fail(VP_EINVAL, "bad LvT configuration");
   if (cfg->video.num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
+  if (cfg->norm_policy != 0 && cfg->norm_policy != 1)
+    return fail(VP_ENOTSUP, "norm_policy must be 0 ('pre') or 1 ('primer_hybrid', the text tower's)");
   vp_clip* c = new vp_clip();
   int rc = c->init(&cfg->video, device, "vision_encoder/");
+  if (!rc) rc = check_pooler_dims(cfg->video);  // after the encoder's own refusals (dim_per_head, bf16 widths)
   if (rc) {
-    delete c;
+    wrap_destroy(c);
     return rc;
   }
   c->cfg = *cfg;
@@ -435,6 +448,7 @@ int clip_video_chunk(vp_clip* c, const void* video, int in_dtype, int64_t B, int
   char* wsv = static_cast<char*>(workspace) + vf.L.inner;
   Fwd f;
   f.s = s; f.bf = bf; f.M = Mp; f.D = D; f.NH = NH; f.cap = v.atten_logit_cap;
+  f.f32_two_chains = f32_two_chains(v);
   f.hb = wsv + Lv.hbuf; f.big = wsv + Lv.big;
   f.st_part = reinterpret_cast<float*>(wsv + Lv.st_part);
   f.ln_rs = reinterpret_cast<float*>(wsv + Lv.ln_rs);
@@ -517,12 +531,14 @@ int vp_clip_encode_text(vp_clip* c, const int32_t* ids, const float* paddings, i
   f.s = s; f.bf = bf; f.M = (int)w.Mt; f.D = D; f.NH = v.num_heads; f.cap = v.atten_logit_cap;
   f.causal = c->cfg.enable_causal_atten ? 1 : 0;
   f.xs_f32 = true;
+  f.f32_two_chains = f32_two_chains(v);
   f.small_m = w.small;
   f.hb = ws + w.hb; f.big = ws + w.big;
   f.pf = &c->video->prof;
   f.cls_all = PC_ATTN_TEXT;  // the whole text tower in one profiler class ("text_tower"), so the vision GEMM
                              // classes (and bench.py's dominant-kernel roofline) hold the vision launches only
-  int rc = f.run_stack(c->text, x, (int)Q, (int)L + 1, pad, 4 * D, PC_ATTN_TEXT, ATT_TEXT, false, true);
+  int rc = f.run_stack(c->text, x, (int)Q, (int)L + 1, pad, 4 * D, PC_ATTN_TEXT, ATT_TEXT, false, true,
+                       c->cfg.norm_policy == 1);
   if (rc) return rc;
   // unimodal_ln on the CLS rows, then L2 (encoders.py:752-758, :905-908)
   VP_HIP(ln_l2_rows(static_cast<float*>(x) + (size_t)L * D, 0, (int64_t)(L + 1) * D, (int)Q, D, c->uln_g,
@@ -545,8 +561,9 @@ int vp_classifier_create(const vp_config* cfg, int num_classes, int device, vp_c
   if (cfg->num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
   vp_classifier* c = new vp_classifier();
   int rc = c->init(cfg, device, "encoder/");
+  if (!rc) rc = check_pooler_dims(*cfg);
   if (rc) {
-    delete c;
+    wrap_destroy(c);
     return rc;
   }
   c->cfg = *cfg;
@@ -692,13 +709,15 @@ int vp_dev_pool_split_u(const float* U_host, int64_t H, int64_t D, uint16_t* ut_
 
 int vp_dev_pool_chunks(int64_t S) { return S < 1 || S > 0x7fffffff ? -1 : vp::pool_chunks((int)S); }
 
-// logits [rows/S][H][S] = x [rows][D] . U [H][D]; Ut: the split of vp_dev_pool_split_u on the device, or NULL
-int vp_dev_pool_logits(const void* x, int in_dtype, int64_t rows, int64_t S, int64_t D, const float* U,
-                       const void* Ut, int64_t H, float* logits, void* stream) {
+// The three entry points below come in two ranges of D: the plain names stop at 1024, as they always have (their
+// refusals are pinned by tests), the *_wide names at vp::kPoolMaxD (Giant's 1408 = 11 x 128).
+static int dev_pool_logits(const void* x, int in_dtype, int64_t rows, int64_t S, int64_t D, const float* U,
+                           const void* Ut, int64_t H, float* logits, void* stream, int64_t max_d) {
   if (!x || !U || !logits) return fail(VP_EINVAL, "null argument");
   if (!float_dtype(in_dtype)) return fail(VP_EINVAL, "bad dtype");
   if (rows < 1 || S < 1 || rows % S) return fail(VP_EINVAL, "pool_logits: rows must be a positive multiple of S");
-  if (D < 64 || D % 64 || D > 1024) return fail(VP_EINVAL, "pool_logits: D must be a multiple of 64, at most 1024");
+  if (D < 64 || D % 64 || D > max_d)
+    return fail(VP_EINVAL, "pool_logits: D must be a multiple of 64, at most " + std::to_string(max_d));
   if (H < 1 || H > 16) return fail(VP_EINVAL, "pool_logits: 1 <= H <= 16");
   if (rows / 64 + 1 > 0x7fffffff) return fail(VP_EINVAL, "pool_logits: too many rows");
   VP_HIP(vp::pool_logits(x, in_dtype == VP_BF16, rows, (int)S, (int)D, U, (const vp::bf16_t*)Ut, (int)H, logits,
@@ -706,19 +725,41 @@ int vp_dev_pool_logits(const void* x, int in_dtype, int64_t rows, int64_t S, int
   return VP_OK;
 }
 
-// stats [G*H][2] = (max, 1/sum exp(l - max)), z [G][H][D] = sum_s softmax(logits)[g][h][s] x[g*S+s];
-// zpart: scratch of [G][vp_dev_pool_chunks(S)][H][D] floats
-int vp_dev_pool_softmax_wsum(const void* x, int in_dtype, int64_t G, int64_t S, int64_t D, int64_t H,
-                             const float* logits, float* stats, float* zpart, float* z, void* stream) {
+// logits [rows/S][H][S] = x [rows][D] . U [H][D]; Ut: the split of vp_dev_pool_split_u on the device, or NULL
+int vp_dev_pool_logits(const void* x, int in_dtype, int64_t rows, int64_t S, int64_t D, const float* U,
+                       const void* Ut, int64_t H, float* logits, void* stream) {
+  return dev_pool_logits(x, in_dtype, rows, S, D, U, Ut, H, logits, stream, 1024);
+}
+int vp_dev_pool_logits_wide(const void* x, int in_dtype, int64_t rows, int64_t S, int64_t D, const float* U,
+                            const void* Ut, int64_t H, float* logits, void* stream) {
+  return dev_pool_logits(x, in_dtype, rows, S, D, U, Ut, H, logits, stream, vp::kPoolMaxD);
+}
+
+static int dev_pool_softmax_wsum(const void* x, int in_dtype, int64_t G, int64_t S, int64_t D, int64_t H,
+                                 const float* logits, float* stats, float* zpart, float* z, void* stream,
+                                 int64_t block, int64_t max_d) {
   if (!x || !logits || !stats || !zpart || !z) return fail(VP_EINVAL, "null argument");
   if (!float_dtype(in_dtype)) return fail(VP_EINVAL, "bad dtype");
   if (G < 1 || S < 1 || G * S > 0x7fffffff) return fail(VP_EINVAL, "pool_softmax_wsum: bad G or S");
-  if (D < 256 || D % 256 || D > 1024)
-    return fail(VP_EINVAL, "pool_softmax_wsum: D must be a multiple of 256, at most 1024");
+  if (D < block || D % block || D > max_d)
+    return fail(VP_EINVAL, "pool_softmax_wsum: D must be a multiple of " + std::to_string(block) + ", at most " +
+                               std::to_string(max_d));
   if (H < 1 || H > 16) return fail(VP_EINVAL, "pool_softmax_wsum: 1 <= H <= 16");
   VP_HIP(vp::pool_softmax_wsum(x, in_dtype == VP_BF16, (int)G, (int)S, (int)D, (int)H, logits, stats, zpart, z,
                                static_cast<hipStream_t>(stream)));
   return VP_OK;
+}
+
+// stats [G*H][2] = (max, 1/sum exp(l - max)), z [G][H][D] = sum_s softmax(logits)[g][h][s] x[g*S+s];
+// zpart: scratch of [G][vp_dev_pool_chunks(S)][H][D] floats
+int vp_dev_pool_softmax_wsum(const void* x, int in_dtype, int64_t G, int64_t S, int64_t D, int64_t H,
+                             const float* logits, float* stats, float* zpart, float* z, void* stream) {
+  return dev_pool_softmax_wsum(x, in_dtype, G, S, D, H, logits, stats, zpart, z, stream, 256, 1024);
+}
+// D = 128 k: an odd k ends in a 128-wide column block
+int vp_dev_pool_softmax_wsum_wide(const void* x, int in_dtype, int64_t G, int64_t S, int64_t D, int64_t H,
+                                  const float* logits, float* stats, float* zpart, float* z, void* stream) {
+  return dev_pool_softmax_wsum(x, in_dtype, G, S, D, H, logits, stats, zpart, z, stream, 128, vp::kPoolMaxD);
 }
 
 // splits == 0: small_gemm (batch matrices at strides sA / sW / sB / sO); splits >= 1: small_gemm_splitk
@@ -743,16 +784,39 @@ int vp_dev_small_gemm(const float* A, int64_t lda, int64_t sA, const float* Wt, 
   return VP_OK;
 }
 
+static int dev_ln_l2_rows(const void* x, int in_dtype, int64_t stride, int64_t rows, int64_t D, const float* gamma,
+                          const float* beta, int do_l2, float* out, void* stream, int64_t max_d) {
+  if (!x || !out || (gamma && !beta)) return fail(VP_EINVAL, "null argument");
+  if (!float_dtype(in_dtype)) return fail(VP_EINVAL, "bad dtype");
+  if (D < 1 || D > max_d) return fail(VP_EINVAL, "ln_l2_rows: 1 <= D <= " + std::to_string(max_d));
+  if (rows < 1 || rows > 0x7fffffff || stride < D) return fail(VP_EINVAL, "ln_l2_rows: rows >= 1 and stride >= D");
+  VP_HIP(vp::ln_l2_rows(x, in_dtype == VP_BF16, stride, (int)rows, (int)D, gamma, beta, do_l2, out,
+                        static_cast<hipStream_t>(stream)));
+  return VP_OK;
+}
+
 // out [rows][D] fp32 = LayerNorm (gamma = 1 + scale, beta; skipped when gamma is NULL) then L2 (if do_l2) of
 // the rows x + r * stride
 int vp_dev_ln_l2_rows(const void* x, int in_dtype, int64_t stride, int64_t rows, int64_t D, const float* gamma,
                       const float* beta, int do_l2, float* out, void* stream) {
-  if (!x || !out || (gamma && !beta)) return fail(VP_EINVAL, "null argument");
-  if (!float_dtype(in_dtype)) return fail(VP_EINVAL, "bad dtype");
-  if (D < 1 || D > 1024) return fail(VP_EINVAL, "ln_l2_rows: 1 <= D <= 1024");
-  if (rows < 1 || rows > 0x7fffffff || stride < D) return fail(VP_EINVAL, "ln_l2_rows: rows >= 1 and stride >= D");
-  VP_HIP(vp::ln_l2_rows(x, in_dtype == VP_BF16, stride, (int)rows, (int)D, gamma, beta, do_l2, out,
-                        static_cast<hipStream_t>(stream)));
+  return dev_ln_l2_rows(x, in_dtype, stride, rows, D, gamma, beta, do_l2, out, stream, 1024);
+}
+int vp_dev_ln_l2_rows_wide(const void* x, int in_dtype, int64_t stride, int64_t rows, int64_t D, const float* gamma,
+                           const float* beta, int do_l2, float* out, void* stream) {
+  return dev_ln_l2_rows(x, in_dtype, stride, rows, D, gamma, beta, do_l2, out, stream, vp::kPoolMaxD);
+}
+
+// norm_policy 'primer_hybrid': xs [rows][D] fp32 += LayerNorm(y [rows][D] (fp32 / bf16) * (1 - pad [rows])) in
+// place; gamma = 1 + scale; pad may be NULL; D = 128 k as vp_op_layernorm takes
+int vp_dev_layernorm_residual(const void* y, int y_dtype, int64_t rows, int64_t D, const float* gamma,
+                              const float* beta, const float* pad, float* xs, void* stream) {
+  if (!y || !gamma || !beta || !xs) return fail(VP_EINVAL, "null argument");
+  if (!float_dtype(y_dtype)) return fail(VP_EINVAL, "bad dtype");
+  if (rows < 1 || rows > 0x7fffffff) return fail(VP_EINVAL, "layernorm_residual: bad rows");
+  if (D < 128 || D % 128 || (D > 1536 && D != 2048))
+    return fail(VP_ENOTSUP, "layernorm_residual: D must be a multiple of 128 up to 1536, or 2048");
+  VP_HIP(vp::layernorm_residual(y, y_dtype == VP_BF16, (int)rows, (int)D, gamma, beta, pad, xs,
+                                static_cast<hipStream_t>(stream)));
   return VP_OK;
 }
 
@@ -783,7 +847,7 @@ int vp_dev_pooler(int kind, void* handle, const void* feat, int64_t G, int64_t S
   if (G < 1 || S < 1 || G * S > 0x7fffffff) return fail(VP_EINVAL, "pooler: bad G or S");
   const vp_config& v = w->video->cfg;
   const int D = v.model_dim, NH = v.num_heads;
-  if (D % 256 || D > 1024) return fail(VP_ENOTSUP, "pooler kernels need model_dim % 256 == 0, at most 1024");
+  if (int rc = check_pooler_dims(v)) return rc;
   const DevPoolWs L = dev_pool_ws(G, S, D, NH, w->pool.dp);
   if (!scratch) {
     *scratch_bytes = L.total;

@@ -52,6 +52,9 @@ struct LayerW {  // one transformer layer, packed
   void* wpost = nullptr; // [D][D]    (out d, in n*H+h)
   float* bpost = nullptr;
   float *ln1_g = nullptr, *ln1_b = nullptr, *ln2_g = nullptr, *ln2_b = nullptr;
+  // norm_policy 'primer_hybrid': ln1 / ln2 are the pre_layer_norms, these the post_layer_norms of the attention
+  // and FFN sublayers (gamma = 1 + scale), applied before the residual (layernorm_residual)
+  float *pn1_g = nullptr, *pn1_b = nullptr, *pn2_g = nullptr, *pn2_b = nullptr;
   void* w1 = nullptr;    // [F][D]
   float* b1 = nullptr;
   // bf16 handles fold LN1 / LN2 into the consuming GEMM (EPI_*_LN): wqkv / w1 hold
@@ -127,19 +130,27 @@ namespace vpi {
 
 inline bool is_bf16(const vp_handle* h) { return h->bf16(); }
 
-// the 16 leaves of a scanned StackedTransformer (layers.py:940-1041) under `pre` (".../x_layers/")
-inline void add_stack_expected(ParamStore& ps, const std::string& pre, int64_t L, int64_t D, int64_t F, int64_t NH) {
+// the 16 leaves of a scanned StackedTransformer (layers.py:940-1041) under `pre` (".../x_layers/"); primer
+// (norm_policy 'primer_hybrid', layers.py:347-351): 20, a pre_layer_norm and a post_layer_norm pair in place of each
+// layer_norm pair
+inline void add_stack_expected(ParamStore& ps, const std::string& pre, int64_t L, int64_t D, int64_t F, int64_t NH,
+                               bool primer = false) {
   const int64_t DH = D / NH;
-  ps.expect(pre + "layer_norm/scale", {L, D});
-  ps.expect(pre + "layer_norm/bias", {L, D});
+  auto add_ln = [&](const std::string& at) {
+    for (const char* ln : {"pre_layer_norm", "post_layer_norm", "layer_norm"}) {
+      if (primer == !std::strcmp(ln, "layer_norm")) continue;
+      ps.expect(at + ln + "/scale", {L, D});
+      ps.expect(at + ln + "/bias", {L, D});
+    }
+  };
+  add_ln(pre);
   for (const char* qkv : {"query", "key", "value"}) {
     ps.expect(pre + "self_attention/" + qkv + "/w", {L, D, NH, DH});
     ps.expect(pre + "self_attention/" + qkv + "/b", {L, NH, DH});
   }
   ps.expect(pre + "self_attention/post/w", {L, D, NH, DH});
   ps.expect(pre + "self_attention/post/b", {L, D});
-  ps.expect(pre + "ff_layer/layer_norm/scale", {L, D});
-  ps.expect(pre + "ff_layer/layer_norm/bias", {L, D});
+  add_ln(pre + "ff_layer/");
   ps.expect(pre + "ff_layer/ffn_layer1/linear/kernel", {L, D, F});
   ps.expect(pre + "ff_layer/ffn_layer1/linear/bias", {L, F});
   ps.expect(pre + "ff_layer/ffn_layer2/linear/kernel", {L, F, D});
@@ -186,13 +197,15 @@ enum QkvExtra {
 // LayerNorms run as kernels (ln*_g / ln*_b).  The row-major q|k|v copy is always kept: it serves the
 // unfused attention paths (other patch grids, frame paddings, caps outside the fast range).
 inline int pack_stack(ParamStore& ps, bool bf16, const std::string& pre, int L, int64_t D, int64_t F, int NH, bool fold,
-                      std::vector<LayerW>& out, QkvExtra extra = QKV_PLAIN) {
+                      std::vector<LayerW>& out, QkvExtra extra = QKV_PLAIN, bool primer = false) {
   const bool qk_perm = extra == QKV_PER_HEAD;
   const float qscale = 1.0f / std::sqrt((float)(D / NH));  // layers.py:576-583
-  const auto& lng = ps.data(pre + "layer_norm/scale");
-  const auto& lnb = ps.data(pre + "layer_norm/bias");
-  const auto& ln2g = ps.data(pre + "ff_layer/layer_norm/scale");
-  const auto& ln2b = ps.data(pre + "ff_layer/layer_norm/bias");
+  if (primer && fold) return fail(VP_ENOTSUP, "norm_policy 'primer_hybrid' runs with unfolded LayerNorms only");
+  const std::string ln = primer ? "pre_layer_norm/" : "layer_norm/";
+  const auto& lng = ps.data(pre + ln + "scale");
+  const auto& lnb = ps.data(pre + ln + "bias");
+  const auto& ln2g = ps.data(pre + "ff_layer/" + ln + "scale");
+  const auto& ln2b = ps.data(pre + "ff_layer/" + ln + "bias");
   const std::vector<float>* wq[3] = {&ps.data(pre + "self_attention/query/w"),
                                      &ps.data(pre + "self_attention/key/w"),
                                      &ps.data(pre + "self_attention/value/w")};
@@ -265,6 +278,17 @@ inline int pack_stack(ParamStore& ps, bool bf16, const std::string& pre, int L, 
     if ((rc = ps.upload_f32(g1, &lw.ln1_g)) || (rc = ps.upload_f32(be1, &lw.ln1_b)) ||
         (rc = ps.upload_f32(g2, &lw.ln2_g)) || (rc = ps.upload_f32(be2, &lw.ln2_b)))
       return rc;
+    if (primer) {
+      const std::string post[2] = {pre + "post_layer_norm/", pre + "ff_layer/post_layer_norm/"};
+      float** dst[2][2] = {{&lw.pn1_g, &lw.pn1_b}, {&lw.pn2_g, &lw.pn2_b}};
+      for (int i = 0; i < 2; ++i) {
+        const auto& sc = ps.data(post[i] + "scale");
+        const auto& bi = ps.data(post[i] + "bias");
+        std::vector<float> g(D), b(bi.begin() + (size_t)l * D, bi.begin() + (size_t)(l + 1) * D);
+        for (int64_t d = 0; d < D; ++d) g[d] = sc[(size_t)l * D + d] + 1.0f;
+        if ((rc = ps.upload_f32(g, dst[i][0])) || (rc = ps.upload_f32(b, dst[i][1]))) return rc;
+      }
+    }
     std::vector<float> t1((size_t)F * D), t2((size_t)D * F);
     const float* w1l = w1.data() + (size_t)l * D * F;  // [D][F]
     for (int64_t k = 0; k < D; ++k)
@@ -600,8 +624,11 @@ struct Fwd {
   // pre-LN transformer layers (layers.py:749-872) over num_seq contiguous sequences of S rows of
   // the residual stream xs (in place).  fold: LN1/LN2 folded into the q|k|v / ffn1 GEMMs, with
   // (rstd, -mean*rstd) of xs already in ln_rs on entry.  relu: ReLU FFN (text tower), else GELU.
+  // primer: norm_policy 'primer_hybrid' (layers.py:388-430, :819-860) over an fp32 residual stream, unfolded: each
+  // sublayer is xs += post_layer_norm(f(pre_layer_norm(xs))), so the post and ffn_layer2 GEMMs store plainly (the
+  // q|k|v projection's epilogue) and layernorm_residual adds the normalised result to xs.
   int run_stack(std::vector<LayerW>& layers, void* xs, int num_seq, int S, const float* pad, int F, int acls,
-                int kind, bool fold, bool relu) {
+                int kind, bool fold, bool relu, bool primer = false) {
     using namespace vp;
     const double dM = M, dD = D, dF = F, dE = bf ? 2.0 : 4.0;
     auto gbytes = [&](double K, double N, double outb, double resid) { return gemm_bytes(dM, K, N, dE, outb, resid); };
@@ -611,6 +638,7 @@ struct Fwd {
     const bool xbf = bf && !xs_f32;  // residual stream dtype
     const int epi_resid = xbf ? EPI_RESID_BF16 : EPI_RESID_F32;
     const int epi_resid_ffn = xbf ? EPI_RESID_FFN_BF16 : EPI_RESID_FFN;
+    if (primer && (fold || xbf)) return fail(VP_ENOTSUP, "primer_hybrid needs an unfolded stack over an fp32 stream");
     // temporal attention fused into the q|k|v projection (vp_kernels.h EPI_*_TATTN_LN): T = 16
     // frames (one 16-row MFMA block per sequence), dh = 64, no key paddings, max-free cap; the
     // unfused pair stays for every other temporal case (frame paddings, T != 16, other caps)
@@ -650,9 +678,18 @@ struct Fwd {
       }
       if (!tattn) VP_HIP(rec(acls, aflops, abytes, [&] {
         return launch_attention(kind, bf, big, hb, num_seq, S, NH, cap, pad, causal, sblk, s, D / NH); }));
-      VP_HIP(rec(PC_GEMM_POST, 2.0 * dM * dD * dD, gbytes(dD, dD, dE, dE), [&] {
-        return gemm(fold ? EPI_RESID_BF16_ST : epi_resid, hb, D, lw.wpost, D, xs, D, lw.bpost, xs, nullptr, 1,
-                    nullptr); }));
+      if (primer) {
+        // the attention output is this GEMM's A, so its result goes to `big` (q|k|v are consumed); no paddings
+        // on the attention sublayer (layers.py:846-855)
+        VP_HIP(rec(PC_GEMM_POST, 2.0 * dM * dD * dD, gbytes(dD, dD, dE, 0), [&] {
+          return gemm(EPI_BF16, hb, D, lw.wpost, D, big, D, lw.bpost, nullptr, nullptr, 1, nullptr); }));
+        VP_HIP(rec(PC_LAYERNORM, 0.0, dM * dD * (dE + 8.0), [&] {
+          return layernorm_residual(big, bf, M, D, lw.pn1_g, lw.pn1_b, nullptr, static_cast<float*>(xs), s); }));
+      } else {
+        VP_HIP(rec(PC_GEMM_POST, 2.0 * dM * dD * dD, gbytes(dD, dD, dE, dE), [&] {
+          return gemm(fold ? EPI_RESID_BF16_ST : epi_resid, hb, D, lw.wpost, D, xs, D, lw.bpost, xs, nullptr, 1,
+                      nullptr); }));
+      }
       if (fold) {  // LN2 folded into ffn_layer1
         VP_HIP(finalize());
         VP_HIP(rec(PC_GEMM_FFN1, 2.0 * dM * dD * dF, gbytes(dD, dF, dE, 0), [&] {
@@ -664,6 +701,15 @@ struct Fwd {
         VP_HIP(rec(PC_GEMM_FFN1, 2.0 * dM * dD * dF, gbytes(dD, dF, dE, 0), [&] {
           return gemm(relu ? EPI_RELU_BF16 : EPI_GELU_BF16, hb, D, lw.w1, F, big, F, lw.b1, nullptr, nullptr, 1,
                       pad); }));
+      }
+      if (primer) {
+        // ffn_layer2 into hb (ffn_layer1 has consumed the pre_layer_norm output there); the padding multiply
+        // (layers.py:409-410) is layernorm_residual's, ahead of its LayerNorm
+        VP_HIP(rec(PC_GEMM_FFN2, 2.0 * dM * dF * dD, gbytes(dF, dD, dE, 0), [&] {
+          return gemm(EPI_BF16, big, F, lw.w2, D, hb, D, lw.b2, nullptr, nullptr, 1, nullptr); }));
+        VP_HIP(rec(PC_LAYERNORM, 0.0, dM * dD * (dE + 8.0), [&] {
+          return layernorm_residual(hb, bf, M, D, lw.pn2_g, lw.pn2_b, pad, static_cast<float*>(xs), s); }));
+        continue;
       }
       const bool st = fold && !last;  // the next layer's LN1 statistics
       const int epi_ffn2 = lw.ffn_blk && fold ? (st ? EPI_RESID_FFN_BF16_ST_BLK : EPI_RESID_FFN_BF16_BLK)

@@ -168,6 +168,11 @@ hipError_t patchify(const void* video, int in_dtype, void* patches, int out_is_b
 hipError_t layernorm(const void* x, int in_is_bf16, int rows, int D, const float* gamma,
                      const float* beta, void* out, int out_is_bf16, int perm, int T, int Nsp,
                      const float* add, hipStream_t s, float* out_rs = nullptr);
+// norm_policy 'primer_hybrid' (layers.py:409-425, :846-855): xs[r] += LayerNorm(y[r] * (1 - pad[r])) in place on the
+// fp32 residual stream; y fp32 or bf16 rows of D = 128 k (layernorm's widths), gamma = 1 + scale, pad optional
+// [rows] (1 = padded token: the row gets xs + beta)
+hipError_t layernorm_residual(const void* y, int y_is_bf16, int rows, int D, const float* gamma, const float* beta,
+                              const float* pad, float* xs, hipStream_t s);
 // f32 (in_dtype 0) / uint8 (2, normalised /255) frames -> bf16 frames, n values, the patchify kernels'
 // per-value conversion (for the fused patch embedding)
 hipError_t video_to_bf16(const void* video, int in_dtype, bf16_t* out, int64_t n, hipStream_t s);
@@ -191,6 +196,8 @@ hipError_t attention_long_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S,
 // bf16 (in_is_bf16, dh 64) or fp32 (dh 64 or 88)
 hipError_t attention_masked(const void* qkv, void* o, int in_is_bf16, int num_seq, int S, int heads,
                             float cap, const float* key_pad, int causal, hipStream_t s, int dh = 64);
+// widest rows the pooler kernels take (pool_logits: D = 64 k; pool_softmax_wsum: D = 128 k; ln_l2_rows: any D)
+constexpr int kPoolMaxD = 1536;
 // contrastive pooler: logits[g][h][s] = x[g*S+s] . U[h]; then softmax per (g,h) and
 // z[g][h][:] = sum_s p x (zpart scratch: [G][pool_chunks(S)][H][D], stats [G*H][2])
 // (bf16 x with Ut = [32][D] bf16 (U_hi | U_lo | 0) and S % 32 == 0: MFMA kernel)

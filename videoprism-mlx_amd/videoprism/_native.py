@@ -60,7 +60,11 @@ class vp_clip_config(ctypes.Structure):
         ("vocabulary_size", c_int32),
         ("num_unimodal_layers", c_int32),
         ("enable_causal_atten", c_int32),
+        ("norm_policy", c_int32),  # text tower: 0 'pre' (the default), 1 'primer_hybrid'
     ]
+
+
+NORM_POLICIES = {"pre": 0, "primer_hybrid": 1}
 
 
 # name -> (restype, argtypes)
@@ -169,6 +173,15 @@ _SIGNATURES = {
                                   c_void_p, c_void_p]),
     "vp_dev_text_embed": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p,
                                   c_float, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    # the same three over D up to 1536 (Giant's 1408), and the primer_hybrid LayerNorm-then-residual kernel
+    "vp_dev_pool_logits_wide": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                        c_void_p, c_void_p]),
+    "vp_dev_pool_softmax_wsum_wide": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vp_dev_ln_l2_rows_wide": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int,
+                                       c_void_p, c_void_p]),
+    "vp_dev_layernorm_residual": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
     "vp_dev_pooler": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
                               POINTER(c_size_t), c_void_p]),
 }
@@ -406,17 +419,19 @@ def dev_pool_chunks(S) -> int:
     return n
 
 
-def dev_pool_logits(x, S, U, Ut, logits, stream=None):
-    """logits [rows/S][H][S] fp32 = x [rows, D] (fp32 / bf16) . U [H, D]; Ut: the uploaded split or None."""
+def dev_pool_logits(x, S, U, Ut, logits, stream=None, wide=False):
+    """logits [rows/S][H][S] fp32 = x [rows, D] (fp32 / bf16) . U [H, D]; Ut: the uploaded split or None.
+    wide: the entry point that takes D up to 1536 (the plain one stops at 1024)."""
     rows, D = x.shape
-    call("vp_dev_pool_logits", _ptr(x), _prec(x), rows, S, D, _ptr(U), _ptr(Ut), U.shape[0], _ptr(logits),
+    call("vp_dev_pool_logits_wide" if wide else "vp_dev_pool_logits", _ptr(x), _prec(x), rows, S, D, _ptr(U), _ptr(Ut), U.shape[0], _ptr(logits),
          _stream(stream))
     return logits
 
 
-def dev_pool_softmax_wsum(x, G, S, H, logits, stats, zpart, z, stream=None):
-    """stats [G*H, 2] = (max, 1/sum exp), z [G, H, D] = softmax(logits [G, H, S]) . x [G*S, D]."""
-    call("vp_dev_pool_softmax_wsum", _ptr(x), _prec(x), G, S, x.shape[1], H, _ptr(logits), _ptr(stats), _ptr(zpart),
+def dev_pool_softmax_wsum(x, G, S, H, logits, stats, zpart, z, stream=None, wide=False):
+    """stats [G*H, 2] = (max, 1/sum exp), z [G, H, D] = softmax(logits [G, H, S]) . x [G*S, D].
+    wide: D = 128 k up to 1536 (the plain entry point: 256 k up to 1024)."""
+    call("vp_dev_pool_softmax_wsum_wide" if wide else "vp_dev_pool_softmax_wsum", _ptr(x), _prec(x), G, S, x.shape[1], H, _ptr(logits), _ptr(stats), _ptr(zpart),
          _ptr(z), _stream(stream))
     return z
 
@@ -429,11 +444,21 @@ def dev_small_gemm(A, lda, sA, Wt, sW, bias, sB, out, ldo, sO, M, N, K, batch=1,
     return out
 
 
-def dev_ln_l2_rows(x, stride, rows, D, gamma1p, beta, do_l2, out, stream=None):
-    """out [rows, D] fp32 = LayerNorm (skipped if gamma1p is None) and / or L2 of rows x[r * stride : +D]."""
-    call("vp_dev_ln_l2_rows", _ptr(x), _prec(x), stride, rows, D, _ptr(gamma1p), _ptr(beta), 1 if do_l2 else 0,
+def dev_ln_l2_rows(x, stride, rows, D, gamma1p, beta, do_l2, out, stream=None, wide=False):
+    """out [rows, D] fp32 = LayerNorm (skipped if gamma1p is None) and / or L2 of rows x[r * stride : +D].
+    wide: D up to 1536 (the plain entry point stops at 1024)."""
+    call("vp_dev_ln_l2_rows_wide" if wide else "vp_dev_ln_l2_rows", _ptr(x), _prec(x), stride, rows, D, _ptr(gamma1p), _ptr(beta), 1 if do_l2 else 0,
          _ptr(out), _stream(stream))
     return out
+
+
+def dev_layernorm_residual(y, gamma1p, beta, xs, pad=None, stream=None):
+    """norm_policy 'primer_hybrid': xs [rows, D] fp32 += LayerNorm(y [rows, D] (fp32 / bf16) * (1 - pad [rows])),
+    in place; D = 128 k."""
+    rows, D = y.shape
+    call("vp_dev_layernorm_residual", _ptr(y), _prec(y), rows, D, _ptr(gamma1p), _ptr(beta), _ptr(pad), _ptr(xs),
+         _stream(stream))
+    return xs
 
 
 def dev_text_embed(ids, table, cls, pos, scale, out, pad_in, pad_out, stream=None):

@@ -235,16 +235,18 @@ class Engine(_EngineBase):
         return out, sp
 
 
-def _cached_engine(model, variables, device: int, norm_policy: str, make):
+def _cached_engine(model, variables, device: int, norm_policy: str, make, policies=("pre",)):
     """The engine of `model` (one of the dataclasses below) for this parameter tree, device and
-    dtype: built by make(flat leaves) on first use, kept in model._engines while the tree lives."""
+    dtype: built by make(flat leaves) on first use, kept in model._engines while the tree lives.
+    policies: the norm policies this kind of model runs."""
     p = variables["params"] if isinstance(variables, dict) and "params" in variables else variables
     key = (id(p), device, model.is_bf16)
     ent = model._engines.get(key)
     if ent is not None and ent[0] is p:
         return ent[1]
-    if norm_policy != "pre":
-        raise NotImplementedError("only norm_policy='pre' is implemented (all public configs)")
+    if norm_policy not in policies:
+        raise NotImplementedError(f"norm_policy={norm_policy!r} is not implemented here (implemented: "
+                                  f"{', '.join(repr(p) for p in policies)}; 'primer_hybrid' in the LvT text tower only)")
     flat = params_lib.canonical_params(variables)
     params_lib.validate(flat, model.param_specs())
     eng = make(flat)
@@ -354,7 +356,8 @@ class ClipEngine(_EngineBase):
             video=_vp_config(cfg, self.bf16), num_auxiliary_layers=cfg.get("num_auxiliary_layers", 0),
             vocabulary_size=cfg["vocabulary_size"],
             num_unimodal_layers=cfg["num_unimodal_layers"],
-            enable_causal_atten=1 if cfg.get("enable_causal_atten", True) else 0)
+            enable_causal_atten=1 if cfg.get("enable_causal_atten", True) else 0,
+            norm_policy=_native.NORM_POLICIES[cfg.get("norm_policy", "pre")])
         return (ctypes.byref(c),)
 
     def encode_video(self, video, frame_paddings=None, normalize=True, want_frames=False,
@@ -426,7 +429,8 @@ class FactorizedVideoCLIP:
                     vocabulary_size=self.vocabulary_size,
                     enable_causal_atten=self.enable_causal_atten,
                     num_unimodal_layers=self.num_unimodal_layers, model_dim=self.model_dim,
-                    num_heads=self.num_heads, atten_logit_cap=self.atten_logit_cap)
+                    num_heads=self.num_heads, atten_logit_cap=self.atten_logit_cap,
+                    norm_policy=self.norm_policy)  # the text tower's (encoders.py:899)
 
     def param_specs(self) -> dict:
         return params_lib.clip_leaf_specs(self.config(), scan=True)
@@ -442,7 +446,8 @@ class FactorizedVideoCLIP:
 
     def engine(self, variables, device: int) -> ClipEngine:
         return _cached_engine(self, variables, device, self.norm_policy,
-                              lambda flat: ClipEngine(self.config(), flat, device, self.is_bf16))
+                              lambda flat: ClipEngine(self.config(), flat, device, self.is_bf16),
+                              policies=("pre", "primer_hybrid"))
 
     def apply(self, variables, inputs=None, text_token_ids=None, text_paddings=None,
               train: bool = False, normalize: bool = True,

@@ -88,6 +88,13 @@ def videoprism_lvt_v1_large(text_tokenizer: str = "c4_en"):
     return encoders.FactorizedVideoCLIP(**config)
 
 
+def videoprism_lvt_v1_giant(text_tokenizer: str = "c4_en"):
+    """models.py:193-199: fp32 only (88-wide heads); its text tower is norm_policy='primer_hybrid'."""
+    config = dict(CONFIGS["videoprism_lvt_v1_giant"])
+    config["vocabulary_size"] = TEXT_TOKENIZERS[text_tokenizer]["vocab_size"]
+    return encoders.FactorizedVideoCLIP(**config)
+
+
 def videoprism_vc_v1_base(num_classes: int):
     """models.py:195-200: FactorizedVideoClassifier on the Base encoder."""
     return encoders.FactorizedVideoClassifier(encoder_params=dict(CONFIGS["videoprism_v1_base"]),

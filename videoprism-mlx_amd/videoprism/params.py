@@ -67,9 +67,22 @@ def encoder_leaf_specs(cfg: dict, scan: bool = True) -> dict[str, tuple[int, ...
     return specs
 
 
-def _stack_specs(prefix: str, L: int, dims: dict, scan: bool) -> dict:
-    out = {}
+def _primer_leaves() -> tuple:
+    """norm_policy 'primer_hybrid' (layers.py:347-351, :388-430, :819-860): a pre_layer_norm and a
+    post_layer_norm pair in place of each layer_norm pair, 20 leaves per layer."""
+    out = []
     for name, shp in _LAYER_LEAVES:
+        head, sep, leaf = name.rpartition("layer_norm/")
+        if sep:
+            out += [(f"{head}{pre}_layer_norm/{leaf}", shp) for pre in ("pre", "post")]
+        else:
+            out.append((name, shp))
+    return tuple(out)
+
+
+def _stack_specs(prefix: str, L: int, dims: dict, scan: bool, norm_policy: str = "pre") -> dict:
+    out = {}
+    for name, shp in (_primer_leaves() if norm_policy == "primer_hybrid" else _LAYER_LEAVES):
         shape = tuple(dims[s] for s in shp)
         if scan:
             out[f"{prefix}/x_layers/{name}"] = (L,) + shape
@@ -106,8 +119,9 @@ def clip_leaf_specs(cfg: dict, scan: bool = True) -> dict[str, tuple[int, ...]]:
     specs[f"{pre}/pooling_attention_layer_norm/bias"] = (D,)
     specs["text_encoder/token_emb/emb_var"] = (cfg["vocabulary_size"], D)
     specs["text_encoder/cls_emb"] = (1, 1, D)
+    # the reference hands norm_policy to the text encoder only (encoders.py:899; :832, :853 are 'pre')
     specs.update(_stack_specs("text_encoder/unimodal_transformer", cfg["num_unimodal_layers"],
-                              {"D": D, "N": nh, "H": D // nh, "F": 4 * D}, scan))
+                              {"D": D, "N": nh, "H": D // nh, "F": 4 * D}, scan, cfg.get("norm_policy", "pre")))
     specs["text_encoder/unimodal_ln/scale"] = (D,)
     specs["text_encoder/unimodal_ln/bias"] = (D,)
     return specs
