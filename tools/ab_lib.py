@@ -6,7 +6,9 @@ device buffers, timed in interleaved rounds, and their outputs compared bitwise.
 """
 import ctypes
 import os
+import shutil
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "videoprism-mlx_amd")]
@@ -88,7 +90,8 @@ def spatial(other):
             f.restype, f.argtypes = nat._SIGNATURES[name]
     st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    for nseq, blk, padded in ((512, True, False), (512, False, False), (37, True, False), (100, True, False), (16, False, True)):
+    for nseq, blk, padded in ((512, True, False), (512, False, False), (37, True, False), (100, True, False), (16, False, True),
+                              (16, True, True)):
         qkv = torch.randn((nseq * 256, 3 * D), generator=g, device=dev)
         qkv[:, :D] *= 0.125
         qkv = qkv.to(torch.bfloat16)
@@ -115,5 +118,48 @@ def spatial(other):
             f"{k} {min(v)*1e3:7.1f} us" for k, v in res.items()), flush=True)
 
 
+def attention(other):
+    """vp_op_attention (bf16, 12 heads unless stated) at the small shapes the whole forwards do not reach: key
+    paddings on the spatial, sequence-packed and temporal kernels (a partly and a fully padded sequence), partial
+    blocks, and the long kernel with and without a tail.  Bitwise this vs other; interleaved timing with the other
+    library loaded a second time (from a copy of the file) beside it, so other vs other2 is the run's own spread."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    tmp = tempfile.NamedTemporaryFile(suffix=".so", delete=False).name
+    shutil.copy(other, tmp)
+    libs = {"this": nat.load(), "other": ctypes.CDLL(other), "other2": ctypes.CDLL(tmp)}
+    os.unlink(tmp)
+    for lib in libs.values():
+        lib.vp_op_attention.restype, lib.vp_op_attention.argtypes = nat._SIGNATURES["vp_op_attention"]
+    st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    cases = [(256, 3, 12, True)] + [(S, 11, 12, p) for S in (40, 64, 130) for p in (True, False)]
+    cases += [(8, 11, 12, True), (16, 11, 12, True), (300, 1, 2, False), (512, 1, 2, False)]
+    for S, nseq, H, padded in cases:
+        D = 64 * H
+        qkv = torch.randn((nseq * S, 3 * D), generator=g, device=dev)
+        qkv[:, :D] *= 0.125
+        qkv = qkv.to(torch.bfloat16)
+        pad = None
+        if padded:  # sequence 1 partly padded, the last one fully
+            pad = torch.zeros(nseq * S, device=dev)
+            pad[S + S // 2 + 1: 2 * S] = 1.0
+            pad[(nseq - 1) * S:] = 1.0
+        outs = {k: torch.full((nseq * S, D), -1.0, device=dev, dtype=torch.bfloat16) for k in libs}
+
+        def run(k):
+            assert libs[k].vp_op_attention(1, ptr(qkv), ptr(outs[k]), nseq, S, H, 50.0, ptr(pad), st()) == 0
+        for k in libs:
+            run(k)
+        torch.cuda.synchronize()
+        same = bool(torch.equal(outs["this"].view(torch.int16), outs["other"].view(torch.int16)))
+        res = {k: [] for k in libs}
+        for _ in range(5):
+            for k in libs:
+                res[k].append(timeit(lambda k=k: run(k)))
+        print(f"attention S={S} nseq={nseq} heads={H} padded={padded}: bitwise this == other {same}; " + " | ".join(
+            f"{k} {min(v)*1e3:7.1f} us" for k, v in res.items()), flush=True)
+
+
 if __name__ == "__main__":
-    {"tattn": tattn, "spatial": spatial}[sys.argv[1]](sys.argv[2])
+    {"tattn": tattn, "spatial": spatial, "attention": attention}[sys.argv[1]](sys.argv[2])

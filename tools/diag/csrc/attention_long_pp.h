@@ -52,11 +52,11 @@ __global__ __launch_bounds__(kPpThreads, 2) void attn_long_pp_kernel(const bf16_
   bf16x8 qf[2][4];
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
-    const int qr = TAIL ? min(q0 + 32 * b + (lane & 31), S - 1) : q0 + 32 * b + (lane & 31);
-    const bf16_t* qp = base + (int64_t)qr * ld + 8 * half;
+    const int qr = TAIL ? min(q_frag_row(q0 + 32 * b, lane), S - 1) : q_frag_row(q0 + 32 * b, lane);
+    const bf16_t* qp = base + (int64_t)qr * ld;
 #pragma unroll
     for (int kd = 0; kd < 4; ++kd)
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[b][kd]) : "v"(qp + 16 * kd));
+      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[b][kd]) : "v"(q_frag_ptr(qp, kd, half)));
   }
   const int nchunks = TAIL ? (S + kLgChunk - 1) / kLgChunk : S / kLgChunk;
   // piece isV of chunk c: this wave's 8 key rows (K rows 8w.., then V rows 8w..), 1 KiB
@@ -92,17 +92,14 @@ __global__ __launch_bounds__(kPpThreads, 2) void attn_long_pp_kernel(const bf16_
     if (grp) __builtin_amdgcn_s_setprio(1);
   }
 
-  const float c1 = 2.0f * kLog2e / cap;
-  const float c2 = cap * kLog2e;
+  const float c1 = cap_c1(cap), c2 = cap_c2(cap);
   f32x16 y[2][2] = {};
   f32x16 x[2] = {};
   bf16x8 pf[2][2] = {};
   typedef float f2_t __attribute__((ext_vector_type(2)));
   f2_t lsum2[2] = {{0.0f, 0.0f}, {0.0f, 0.0f}};
   const int krow_l = lane & 31;
-  const int g = lane >> 4;
-  const int li = lane & 15;
-  const int trq = li >> 2, trp = li & 3;
+  const int trq = (lane & 15) >> 2;
   const int ntiles = 2 * nchunks;
   const int nphase = 2 * ntiles + 2;
 
@@ -119,11 +116,7 @@ __global__ __launch_bounds__(kPpThreads, 2) void attn_long_pp_kernel(const bf16_
         for (int s = 0; s < 2; ++s) {
           const int key = (tp & 1) * 32 + 16 * s + 4 * half + trq;
 #pragma unroll
-          for (int dh = 0; dh < 2; ++dh) {
-            const int col = 32 * dh + 16 * (g & 1) + 4 * trp;
-            const int cc = col >> 3;
-            vad[s][dh] = (uint32_t)(uintptr_t)VP_LDS_PTR(Vs + key * 128 + ((cc ^ swzV(key)) << 4) + (col & 7) * 2);
-          }
+          for (int dh = 0; dh < 2; ++dh) vad[s][dh] = lds_addr(v_read_at(Vs, key, dh, lane));
         }
         s16x4 vr[2][2][2];
         lds_tr_read8(vr, vad);
@@ -132,8 +125,7 @@ __global__ __launch_bounds__(kPpThreads, 2) void attn_long_pp_kernel(const bf16_
         for (int s = 0; s < 2; ++s) {
 #pragma unroll
           for (int dh = 0; dh < 2; ++dh) {
-            const s16x4 lo = vr[s][dh][0], hi = vr[s][dh][1];
-            const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            const bf16x8 vf = v_frag(vr[s][dh]);
 #pragma unroll
             for (int b = 0; b < 2; ++b) y[b][dh] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[b][s], y[b][dh], 0, 0, 0);
           }
@@ -145,10 +137,7 @@ __global__ __launch_bounds__(kPpThreads, 2) void attn_long_pp_kernel(const bf16_
         bf16x8 kf[4];
         uint32_t kad[4];
 #pragma unroll
-        for (int kd = 0; kd < 4; ++kd) {
-          const int cc = 2 * kd + half;
-          kad[kd] = (uint32_t)(uintptr_t)VP_LDS_PTR(Ks + krow * 128 + ((cc ^ swzK(krow)) << 4));
-        }
+        for (int kd = 0; kd < 4; ++kd) kad[kd] = lds_addr(k_read_at(Ks, krow, kd, half));
         lds_read4_b128(kf, kad);
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
@@ -222,32 +211,26 @@ __global__ __launch_bounds__(kPpThreads, 2) void attn_long_pp_kernel(const bf16_
   }
 }
 
-template <int VAR, bool TAIL>
-hipError_t launch_attn_long_pp_t(const bf16_t* qkv, bf16_t* o, int num_seq, int S, int heads, float cap,
-                                 hipStream_t s) {
-  const void* fn = reinterpret_cast<const void*>(attn_long_pp_kernel<VAR, TAIL>);
-  hipError_t e = ensure_dyn_lds(fn, kPpLds);
-  if (e != hipSuccess) return e;
-  const int nqb = (S + kPpQ - 1) / kPpQ;
-  const int64_t grid = (int64_t)num_seq * heads * nqb;
-  if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  const int xcd_map = grid % 8 == 0 ? 1 : 0;
-  const CapPoly cp = make_cap_poly(cap);
-  VP_NOTE_KERNEL(fn);
-  hipLaunchKernelGGL((attn_long_pp_kernel<VAR, TAIL>), dim3((unsigned)grid), dim3(kPpThreads), kPpLds, s, qkv, o, S,
-                     heads, nqb, cap, xcd_map, cp);
-  return hipGetLastError();
-}
-
 // S >= 512: S % 512 == 0, or TAIL
 template <int VAR>
 hipError_t launch_attn_long_pp(const bf16_t* qkv, bf16_t* o, int num_seq, int S, int heads, float cap,
                                hipStream_t s) {
   if (S < kPpQ || !(cap > 0.0f) || num_seq < 1) return hipErrorInvalidValue;
-  if (S % kPpQ == 0) return launch_attn_long_pp_t<VAR, false>(qkv, o, num_seq, S, heads, cap, s);
-  return launch_attn_long_pp_t<VAR, true>(qkv, o, num_seq, S, heads, cap, s);
+  return with_bool(S % kPpQ != 0, [&](auto tail) {
+    const auto kernel = attn_long_pp_kernel<VAR, decltype(tail)::value>;
+    hipError_t e = ensure_dyn_lds((const void*)kernel, kPpLds);
+    if (e != hipSuccess) return e;
+    const int nqb = (S + kPpQ - 1) / kPpQ;
+    const int64_t grid = (int64_t)num_seq * heads * nqb;
+    if (grid > 0x7fffffff) return hipErrorInvalidValue;
+    const int xcd_map = grid % 8 == 0 ? 1 : 0;
+    const CapPoly cp = make_cap_poly(cap);
+    VP_NOTE_KERNEL(kernel);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kPpThreads), kPpLds, s, qkv, o, S, heads, nqb, cap, xcd_map,
+                       cp);
+    return hipGetLastError();
+  });
 }
-
 
 }  // namespace
 

@@ -11,55 +11,29 @@
 //
 // attention_spatial_bf16: S = 256 (one frame's patch grid), dh = 64.  One workgroup per
 //   (frame, head); K and V (32 KiB each) land in LDS by global_load_lds; 8 waves x 32
-//   queries.  S^T = K.Q^T on v_mfma_f32_32x32x16_bf16 puts one query per lane column; the
-//   bf16 numerators are fed straight back as the B operand of O^T = V^T.P^T (V read with
-//   ds_read_b64_tr_b16), so P never touches LDS and the row sum is lane-local.
+//   queries on the shared 32x32x16 tile (attention_tile.h): P never touches LDS and the row sum is lane-local.
 // attention_temporal_bf16: S = T <= 16 frames.  One wave per (sequence, head), 16x16x32 for
 //   Q.K^T and 16x16x16 for P.V; memory-bound on the qkv rows.
 // attention_seq_bf16: 16 < S <= 256 (clips longer than 16 frames, other patch grids, the text tower with
 //   its causal mask): sequences packed into the spatial kernel's 256-key tile.
-// attention_f32: fp32 path (fprop_dtype=float32), any S <= 256: S >= 128 with 0 < cap <= 50 on
-//   v_mfma_f32_32x32x2f32 (attention_f32_mfma), anything else on a generic online-softmax kernel with exact
-//   tanhf/expf.
-// attention_f32_mfma: fp32, any S >= 1 with 0 < cap <= 50 (max-free softmax; numerators from
-//   capped_exp_f32x16, a tanh fit and a compensated exp2 within a few fp32 ulp); used from S >= 128, by the auxiliary encoder at any S.
-// Which of these (and attention_long.hip's attention_long_bf16 / attention_masked) a stack runs is decided in
-// one place, vp_internal.h choose_attention; first match:
-//   text tower       bf16, 0 < cap <= 50, 16 < S <= 256: seq (causal); otherwise masked (causal)
-//   bf16, other caps masked (cap <= 0 or cap > 50: no max-free softmax)
-//   auxiliary, fp32  0 < cap <= 50: f32_mfma; otherwise masked
-//   auxiliary, bf16  S >= 256: long; S > 16: seq; otherwise temporal
-//   video, fp32      S <= 256: f32; longer: f32_mfma for 0 < cap <= 50, otherwise masked
-//                    (88-wide heads, cap outside (0, 50]: f32 up to S = 224, its LDS limit; longer: masked)
+// attention_f32_mfma: fp32 (fprop_dtype=float32) on v_mfma_f32_32x32x2f32, any S >= 1 with 0 < cap <= 50 (max-free
+//   softmax); the numerators are approximated, not libm's: capped_exp_f32x16, a degree-5 tanh fit and a compensated
+//   exp2, a few fp32 ulp from exp(cap tanh(x / cap)).
+// attention_f32: fp32, S <= 256: S >= 128 with 0 < cap <= 50 goes to attention_f32_mfma; anything else runs a generic
+//   online-softmax kernel (any cap, exact tanhf / expf), which keeps K|V of a sequence in LDS (S <= 256 for 64-wide
+//   heads, S <= 224 for 88-wide ones).
 // The fp32 kernels here take heads of 64 or 88 floats (template parameter DH; 88: the Giant encoder, 1408 / 16); the
 // bf16 kernels are 64-wide only.
-//   video, bf16      S == 256: spatial; S <= 16: temporal; S < 256: seq; longer: masked
+// Which of these (and attention_long.hip's attention_long_bf16 / attention_masked) a stack runs is decided in one
+// place, vp_internal.h choose_attention (its table is stated there and pinned by tests/test_attention_dispatch_cpu.py).
 #include <type_traits>
 
-#include "vp_common.h"
+#include "attention_tile.h"
 #include "vp_kernels.h"
 
 namespace vp {
 
 namespace {
-
-constexpr float kLog2e = 1.4426950408889634f;
-
-// exp(cap * tanh(x / cap)) with tanh(y) = 1 - 2 / (exp(2y) + 1); saturates correctly.
-__device__ __forceinline__ float capped_exp(float x, float two_log2e_over_cap, float cap_log2e) {
-  const float t = __builtin_amdgcn_exp2f(x * two_log2e_over_cap);
-  const float r = __builtin_amdgcn_rcpf(t + 1.0f);
-  return __builtin_amdgcn_exp2f(cap_log2e - 2.0f * cap_log2e * r);
-}
-
-__device__ __forceinline__ int swzK(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ int swzV(int row) { return ((row >> 1) & 1) << 2; }
-
-__device__ __forceinline__ bf16x4 tr_read(const char* p) {
-  s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4*)(p));
-  return bf16x4{v[0], v[1], v[2], v[3]};
-}
 
 // ------------------------------------------------------------------------------------
 // spatial: S = 256, dh = 64
@@ -101,11 +75,10 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_spatial_kernel(
     return qkv + (((int64_t)seq * 16 + (r >> 4)) * (ld >> 5) + (col >> 5)) * 512 + (r & 15) * 32 + (col & 31);
   };
 
-  // ---- this wave's 32 queries as the B operand (lane: q = l&31, d = 16kd + 8(l>>5) + j),
-  // requested ahead of the K/V stream.  hipcc cannot count a plain load against the LDS-DMA
-  // pieces behind it (mixed event kinds: it emits vmcnt(0), draining the stream before the first
-  // key tile), so these are asm loads retired by chunk 0's wait statement, which names qf as
-  // operands (cdna_hip_programming.md §5.7 item 1, form (ii)); tools/check_kernels.py audits the
+  // ---- this wave's 32 queries as the B operand (attention_tile.h q_frag_row / q_frag_ptr, written out), requested
+  // ahead of the K/V stream.  hipcc cannot count a plain load against the LDS-DMA pieces behind it (mixed event
+  // kinds: it emits vmcnt(0), draining the stream before the first key tile), so these are asm loads retired by
+  // chunk 0's wait statement, which names qf as operands (cdna_hip_programming.md §5.7 item 1, form (ii)); tools/check_kernels.py audits the
   // assembly for any compiler access to those registers in between, and the build refuses
   // scratch or spills in every product kernel ----
   const int q0 = w * 32;
@@ -128,9 +101,8 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_spatial_kernel(
     for (int isV = 0; isV < 2; ++isV) {
       const int piece = isV * 32 + cc * 8 + w;
       const int row = (piece & 31) * 8 + (lane >> 3);
-      const int c = (lane & 7) ^ (isV ? swzV(row) : swzK(row));
-      const bf16_t* src = BLK ? blk_at(row, (isV ? 2 : 1) * (int)sec + h * 64 + c * 8)
-                              : base + (int64_t)row * ld + (isV ? 2 * sec : sec) + c * 8;
+      const int c = (lane & 7) ^ (isV ? swzV(row) : swzK(row));  // (attention_tile.h stage_chunk)
+      const bf16_t* src = BLK ? blk_at(row, (isV ? 2 : 1) * (int)sec + h * 64 + c * 8) : stage_src(base, row, ld, sec, isV, 0, c);
       __builtin_amdgcn_global_load_lds(VP_GLB_PTR(src), VP_LDS_PTR(smem + piece * 1024), 16, 0, 0);
     }
   if constexpr (MASK) {  // (padded batches: no streaming)
@@ -160,14 +132,10 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_spatial_kernel(
     all_masked = *allmask != 0;
   }
 
-  const float c1 = 2.0f * kLog2e / cap;
-  const float c2 = cap * kLog2e;
+  const float c1 = cap_c1(cap), c2 = cap_c2(cap);
   f32x16 y0 = {}, y1 = {};
   float lsum = 0.0f;
   const int krow_l = lane & 31;
-  const int g = lane >> 4;
-  const int li = lane & 15;
-  const int trq = li >> 2, trp = li & 3;
 
   // S^T tile of keys kt*32 .. +31: X[key][q]
   auto qk = [&](int kt) {
@@ -175,14 +143,16 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_spatial_kernel(
     const int krow = kt * 32 + krow_l;
 #pragma unroll
     for (int kd = 0; kd < 4; ++kd) {
-      const int c = 2 * kd + half;
-      const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + krow * 128 + ((c ^ swzK(krow)) << 4));
+      const bf16x8 kf = *reinterpret_cast<const bf16x8*>(k_read_at(Ks, krow, kd, half));
       x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kd], x, 0, 0, 0);
     }
     return x;
   };
-  // per-lane V read bases (lds_tr_read8_o): for key = kt 32 + 16 s + 4 half + trq, swzV(key) = ((trq >> 1) & 1) << 2,
-  // so a tile's V addresses are these plus the immediate kt 4096 (+ 2048 s, + 1024 for the upper 4 rows)
+  const int g = lane >> 4;
+  const int li = lane & 15;
+  const int trq = li >> 2, trp = li & 3;
+  // per-lane V read bases of the unrolled unmasked form (a tile's V offset kt 4096 is an immediate there;
+  // attention_tile.h v_read_at with swzV(key) = swzV(trq))
   [[maybe_unused]] uint32_t vb[2];
 #pragma unroll
   for (int dh = 0; dh < 2; ++dh) {
@@ -194,12 +164,11 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_spatial_kernel(
   // OFFT: the tile's V offset kt * 4096 as a compile-time constant (the unrolled unmasked form), or -1 (run time)
   auto pv = [&](int kt, auto OFFT, const f32x16& x) {
     constexpr int voff = decltype(OFFT)::value;
-    // numerators: register i <-> key kt*32 + (i&3) + 8(i>>2) + 4*half (exact three-transcendental
-    // form: the one-transcendental polynomial moved the full-depth LvT-B bf16 embedding across the
-    // 1e-3 bar)
+    // numerators (exact three-transcendental form: the one-transcendental polynomial moved the
+    // full-depth LvT-B bf16 embedding across the 1e-3 bar)
     float p[16];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) p[i] = capped_exp(x[i], c1, c2);
+    for (int i = 0; i < 16; ++i) p[i] = capped_exp_exact(x[i], c1, c2);
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       float e = p[i];
@@ -211,13 +180,7 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_spatial_kernel(
       lsum += e;
     }
     bf16x8 pf[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      uint32_t u[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) u[j] = pack_bf16x2(p[8 * s + 2 * j], p[8 * s + 2 * j + 1]);
-      pf[s] = *reinterpret_cast<bf16x8*>(u);
-    }
+    pack_numerators(p, pf);
     // O^T += V^T . X  (A = V^T via transposed reads, B = P^T numerators).  hipcc puts a vmcnt(0)
     // for the in-flight K/V chunks in front of a visible ds_read_tr (it cannot tell it from a read
     // of a chunk still landing), so the 8 reads are inline asm -- issued together with their
@@ -242,16 +205,7 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_spatial_kernel(
       lds_tr_read8(vr, ad);
     }
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int dh = 0; dh < 2; ++dh) {
-        const s16x4 lo = vr[s][dh][0], hi = vr[s][dh][1];
-        const bf16x8 vf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        if (dh == 0) y0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[s], y0, 0, 0, 0);
-        else y1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[s], y1, 0, 0, 0);
-      }
-    }
+    pv_mfma(vr, pf, y0, y1);
   };
 
   // (a software-pipelined form -- the S^T MFMAs of tile kt+1 issued ahead of tile kt's
@@ -282,18 +236,14 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_spatial_kernel(
   }
   lsum += __shfl_xor(lsum, 32);
   const float inv = 1.0f / lsum;
-  // y_dh[i] = O^T[d = 32dh + (i&3) + 8(i>>2) + 4*half][q = q0 + (l&31)].  Every wave is done with
-  // K/V: the wave's 32 x 64 output tile goes to its 4 KiB of the K region ([q][16-B chunk ^ (q & 7)]),
+  // Every wave is done with K/V: the wave's 32 x 64 output tile goes to its 4 KiB of the K region ([q][16-B chunk ^ (q & 7)]),
   // then 8 lanes per row store whole 128-B segments
   __syncthreads();
   char* st = smem + w * 4096;
   const int ql = lane & 31;
 #pragma unroll
   for (int g4 = 0; g4 < 4; ++g4) {
-    const uint2 v0 = make_uint2(pack_bf16x2(y0[4 * g4] * inv, y0[4 * g4 + 1] * inv),
-                                pack_bf16x2(y0[4 * g4 + 2] * inv, y0[4 * g4 + 3] * inv));
-    const uint2 v1 = make_uint2(pack_bf16x2(y1[4 * g4] * inv, y1[4 * g4 + 1] * inv),
-                                pack_bf16x2(y1[4 * g4 + 2] * inv, y1[4 * g4 + 3] * inv));
+    const uint2 v0 = pack_o_quad(y0, g4, inv), v1 = pack_o_quad(y1, g4, inv);
     *reinterpret_cast<uint2*>(st + ql * 128 + (((g4) ^ (ql & 7)) << 4) + 8 * half) = v0;
     *reinterpret_cast<uint2*>(st + ql * 128 + (((4 + g4) ^ (ql & 7)) << 4) + 8 * half) = v1;
   }
@@ -346,7 +296,7 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_seq_kernel(const bf16_t* _
     const int piece = i * 8 + w;
     const int isV = piece >> 5;
     const int slot = (piece & 31) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ (isV ? swzV(slot) : swzK(slot));
+    const int c = (lane & 7) ^ (isV ? swzV(slot) : swzK(slot));  // (attention_tile.h stage_chunk, stage_src)
     const bf16_t* src = qkv + row_of(slot) * ld + (isV ? 2 * D : D) + h * 64 + c * 8;
     __builtin_amdgcn_global_load_lds(VP_GLB_PTR(src), VP_LDS_PTR(smem + piece * 1024), 16, 0, 0);
   }
@@ -355,9 +305,9 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_seq_kernel(const bf16_t* _
   const int j = q0 / Sp;  // this wave's sequence in the workgroup
   bf16x8 qf[4];
   {
-    const bf16_t* qp = qkv + row_of(q0 + (lane & 31)) * ld + h * 64 + 8 * half;
+    const bf16_t* qp = qkv + row_of(q_frag_row(q0, lane)) * ld + h * 64;
 #pragma unroll
-    for (int kd = 0; kd < 4; ++kd) qf[kd] = *reinterpret_cast<const bf16x8*>(qp + 16 * kd);
+    for (int kd = 0; kd < 4; ++kd) qf[kd] = *reinterpret_cast<const bf16x8*>(q_frag_ptr(qp, kd, half));
   }
   if constexpr (MASK) {
     if (threadIdx.x < kSpS) {
@@ -378,8 +328,7 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_seq_kernel(const bf16_t* _
   const int qt = q0 + (lane & 31) - j * Sp;
   const bool all_masked = MASK && (causal ? kp[q0 + (lane & 31)] != 0.0f : allmask[j] != 0);
 
-  const float c1 = 2.0f * kLog2e / cap;
-  const float c2 = cap * kLog2e;
+  const float c1 = cap_c1(cap), c2 = cap_c2(cap);
   f32x16 y0 = {}, y1 = {};
   float lsum = 0.0f;
   const int krow_l = lane & 31;
@@ -393,16 +342,14 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_seq_kernel(const bf16_t* _
     const int krow = kt * 32 + krow_l;
 #pragma unroll
     for (int kd = 0; kd < 4; ++kd) {
-      const int c = 2 * kd + half;
-      const bf16x8 kf = *reinterpret_cast<const bf16x8*>(Ks + krow * 128 + ((c ^ swzK(krow)) << 4));
+      const bf16x8 kf = *reinterpret_cast<const bf16x8*>(k_read_at(Ks, krow, kd, half));
       x = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kd], x, 0, 0, 0);
     }
-    // register i <-> key slot kt*32 + (i&3) + 8(i>>2) + 4*half
     float p[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int slot = kt * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
-      float e = capped_exp(x[i], c1, c2);
+      float e = capped_exp_exact(x[i], c1, c2);
       if (causal && slot - j * Sp > qt) e = 0.0f;
       if constexpr (MASK) e = all_masked ? 1.0f : (kp[slot] != 0.0f ? 0.0f : e);
       if (slot - j * Sp >= S) e = 0.0f;
@@ -410,13 +357,9 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_seq_kernel(const bf16_t* _
       lsum += e;
     }
     bf16x8 pf[2];
-#pragma unroll
-    for (int sidx = 0; sidx < 2; ++sidx) {
-      uint32_t u[4];
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) u[jj] = pack_bf16x2(p[8 * sidx + 2 * jj], p[8 * sidx + 2 * jj + 1]);
-      pf[sidx] = *reinterpret_cast<bf16x8*>(u);
-    }
+    pack_numerators(p, pf);
+    // every piece has landed (the wait above), so V takes compiler-visible transposed reads (attention_tile.h
+    // v_read_at / pv_mfma, written out)
 #pragma unroll
     for (int sidx = 0; sidx < 2; ++sidx) {
       const int key = kt * 32 + 16 * sidx + 4 * half + trq;
@@ -437,7 +380,6 @@ __global__ __launch_bounds__(kSpThreads, 4) void attn_seq_kernel(const bf16_t* _
   const int slot = q0 + (lane & 31);
   const int t = slot - j * Sp;
   if (t >= S || seq0 + j >= num_seq) return;
-  // y_dh[i] = O^T[d = 32dh + (i&3) + 8(i>>2) + 4*half][query]: 4 consecutive dims per register quad
   bf16_t* op = o + ((int64_t)(seq0 + j) * S + t) * D + h * 64 + 4 * half;
 #pragma unroll
   for (int g4 = 0; g4 < 4; ++g4) {
@@ -509,14 +451,13 @@ __global__ __launch_bounds__(kTpWaves * 64) void attn_temporal_kernel(
       kpad[r] = key < S ? key_pad[(int64_t)seq * S + key] : 1.0f;
     }
   }
-  const float c1 = 2.0f * kLog2e / cap;
-  const float c2 = cap * kLog2e;
+  const float c1 = cap_c1(cap), c2 = cap_c2(cap);
   float p[4];
   float lsum = 0.f;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int key = 4 * g + r;
-    float e = key < S ? capped_exp(x[r], c1, c2) : 0.0f;
+    float e = key < S ? capped_exp_exact(x[r], c1, c2) : 0.0f;
     if constexpr (MASK) e = key < S ? (all_masked ? 1.0f : (kpad[r] != 0.0f ? 0.0f : e)) : 0.0f;
     p[r] = e;
     lsum += e;
@@ -846,12 +787,6 @@ __global__ __launch_bounds__(512) void attn_f32_mfma_kernel(const float* __restr
 hipError_t attention_spatial_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int heads, float cap,
                                   const float* key_pad, hipStream_t s, bool blk) {
   if (!(cap > 0.0f)) return hipErrorInvalidValue;
-  const int mi = (key_pad ? 1 : 0) + (blk ? 2 : 0);
-  const void* fns[4] = {(const void*)attn_spatial_kernel<false, false>, (const void*)attn_spatial_kernel<true, false>,
-                        (const void*)attn_spatial_kernel<false, true>, (const void*)attn_spatial_kernel<true, true>};
-  const void* fn = fns[mi];
-  hipError_t e = ensure_dyn_lds(fn, kSpLds);
-  if (e != hipSuccess) return e;
   const dim3 grid(num_seq * heads);
   // frames in reverse order (the producing GEMM's last-written q|k|v rows first): 2.354-2.358 vs
   // 2.400-2.407 ms/step in the forward (round 3, one box, alternating; round 2 measured it neutral)
@@ -862,19 +797,18 @@ hipError_t attention_spatial_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int
   // O leaves through LDS as whole 128-B row segments (217 -> 209 us at the bench shape); a
   // head-major q|k|v layout measured only 1 % faster and is not used
   const int64_t D = heads * 64;
-  if (blk && (3 * D) % 32) return hipErrorInvalidValue;
-  VP_NOTE_KERNEL(fn);
-#define VP_SPATIAL(M, B)                                                                                        \
-  hipLaunchKernelGGL((attn_spatial_kernel<M, B>), grid, dim3(kSpThreads), kSpLds, s, qkv, o, heads, cap, key_pad, \
-                     rev, 3 * D, (int64_t)64, D)
-  switch (mi) {
-    case 0: VP_SPATIAL(false, false); break;
-    case 1: VP_SPATIAL(true, false); break;
-    case 2: VP_SPATIAL(false, true); break;
-    default: VP_SPATIAL(true, true); break;
-  }
-#undef VP_SPATIAL
-  return hipGetLastError();
+  return with_bool(key_pad != nullptr, [&](auto mask) {
+    return with_bool(blk, [&](auto blocked) {
+      const auto kernel = attn_spatial_kernel<decltype(mask)::value, decltype(blocked)::value>;
+      hipError_t e = ensure_dyn_lds((const void*)kernel, kSpLds);
+      if (e != hipSuccess) return e;
+      if (blk && (3 * D) % 32) return hipErrorInvalidValue;
+      VP_NOTE_KERNEL(kernel);
+      hipLaunchKernelGGL(kernel, grid, dim3(kSpThreads), kSpLds, s, qkv, o, heads, cap, key_pad, rev, 3 * D, (int64_t)64,
+                         D);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t attention_temporal_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S, int heads,
@@ -882,12 +816,12 @@ hipError_t attention_temporal_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, in
   if (!(cap > 0.0f) || S < 1 || S > 16) return hipErrorInvalidValue;
   const int pairs = num_seq * heads;
   const dim3 grid((pairs + kTpWaves - 1) / kTpWaves);
-  VP_NOTE_KERNEL(key_pad ? (const void*)attn_temporal_kernel<true> : (const void*)attn_temporal_kernel<false>);
-  if (key_pad)
-    hipLaunchKernelGGL(attn_temporal_kernel<true>, grid, dim3(kTpWaves * 64), 0, s, qkv, o, pairs, S, heads, cap, key_pad);
-  else
-    hipLaunchKernelGGL(attn_temporal_kernel<false>, grid, dim3(kTpWaves * 64), 0, s, qkv, o, pairs, S, heads, cap, key_pad);
-  return hipGetLastError();
+  return with_bool(key_pad != nullptr, [&](auto mask) {
+    const auto kernel = attn_temporal_kernel<decltype(mask)::value>;
+    VP_NOTE_KERNEL(kernel);
+    hipLaunchKernelGGL(kernel, grid, dim3(kTpWaves * 64), 0, s, qkv, o, pairs, S, heads, cap, key_pad);
+    return hipGetLastError();
+  });
 }
 
 hipError_t attention_seq_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S, int heads, float cap,
@@ -895,19 +829,17 @@ hipError_t attention_seq_bf16(const bf16_t* qkv, bf16_t* o, int num_seq, int S, 
   if (!(cap > 0.0f) || S < 17 || S > kSpS || num_seq < 1) return hipErrorInvalidValue;
   const int Sp = S <= 32 ? 32 : S <= 64 ? 64 : S <= 128 ? 128 : 256;
   const int per = kSpS / Sp;
-  const void* fn = key_pad ? (const void*)attn_seq_kernel<true> : (const void*)attn_seq_kernel<false>;
-  hipError_t e = ensure_dyn_lds(fn, kSqLds);
-  if (e != hipSuccess) return e;
   const int64_t grid = (int64_t)((num_seq + per - 1) / per) * heads;
-  if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  VP_NOTE_KERNEL(fn);
-  if (key_pad)
-    hipLaunchKernelGGL(attn_seq_kernel<true>, dim3((unsigned)grid), dim3(kSpThreads), kSqLds, s, qkv, o, num_seq, S,
-                       Sp, heads, cap, key_pad, causal);
-  else
-    hipLaunchKernelGGL(attn_seq_kernel<false>, dim3((unsigned)grid), dim3(kSpThreads), kSqLds, s, qkv, o, num_seq, S,
-                       Sp, heads, cap, key_pad, causal);
-  return hipGetLastError();
+  return with_bool(key_pad != nullptr, [&](auto mask) {
+    const auto kernel = attn_seq_kernel<decltype(mask)::value>;
+    hipError_t e = ensure_dyn_lds((const void*)kernel, kSqLds);
+    if (e != hipSuccess) return e;
+    if (grid > 0x7fffffff) return hipErrorInvalidValue;
+    VP_NOTE_KERNEL(kernel);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kSpThreads), kSqLds, s, qkv, o, num_seq, S, Sp, heads, cap,
+                       key_pad, causal);
+    return hipGetLastError();
+  });
 }
 
 namespace {
@@ -919,23 +851,16 @@ hipError_t launch_f32_mfma(const float* qkv, float* o, int num_seq, int S, int h
   const int nqb = (S + 255) / 256;
   const int64_t grid = (int64_t)num_seq * heads * nqb;
   if (grid > 0x7fffffff || (int64_t)num_seq * S > 0x7fffffff) return hipErrorInvalidValue;
-  const int mi = (key_pad ? 1 : 0) + (S % 256 ? 2 : 0);
-  const void* fns[4] = {(const void*)attn_f32_mfma_kernel<DH, false, false>, (const void*)attn_f32_mfma_kernel<DH, true, false>,
-                        (const void*)attn_f32_mfma_kernel<DH, false, true>, (const void*)attn_f32_mfma_kernel<DH, true, true>};
-  hipError_t e = ensure_dyn_lds(fns[mi], kLds);
-  if (e != hipSuccess) return e;
-  VP_NOTE_KERNEL(fns[mi]);
-#define VP_F32M(M, T)                                                                                              \
-  hipLaunchKernelGGL((attn_f32_mfma_kernel<DH, M, T>), dim3((unsigned)grid), dim3(512), kLds, s, qkv, o, S, heads, \
-                     nqb, cap, key_pad)
-  switch (mi) {
-    case 0: VP_F32M(false, false); break;
-    case 1: VP_F32M(true, false); break;
-    case 2: VP_F32M(false, true); break;
-    default: VP_F32M(true, true); break;
-  }
-#undef VP_F32M
-  return hipGetLastError();
+  return with_bool(key_pad != nullptr, [&](auto mask) {
+    return with_bool(S % 256 != 0, [&](auto tail) {
+      const auto kernel = attn_f32_mfma_kernel<DH, decltype(mask)::value, decltype(tail)::value>;
+      hipError_t e = ensure_dyn_lds((const void*)kernel, kLds);
+      if (e != hipSuccess) return e;
+      VP_NOTE_KERNEL(kernel);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(512), kLds, s, qkv, o, S, heads, nqb, cap, key_pad);
+      return hipGetLastError();
+    });
+  });
 }
 
 template <int DH>

@@ -4,23 +4,12 @@
 #pragma once
 #include <type_traits>
 
-#include "vp_common.h"
+#include "attention_tile.h"
 #include "vp_kernels.h"
 
 namespace vp {
 
 namespace {
-
-constexpr float kLog2e = 1.4426950408889634f;
-
-__device__ __forceinline__ float capped_exp(float x, float two_log2e_over_cap, float cap_log2e) {
-  const float t = __builtin_amdgcn_exp2f(x * two_log2e_over_cap);
-  const float r = __builtin_amdgcn_rcpf(t + 1.0f);
-  return __builtin_amdgcn_exp2f(cap_log2e - 2.0f * cap_log2e * r);
-}
-
-__device__ __forceinline__ int swzK(int row) { return (row >> 1) & 7; }
-__device__ __forceinline__ int swzV(int row) { return ((row >> 1) & 1) << 2; }
 
 constexpr int kLgThreads = 512;          // 8 waves x 32 queries
 constexpr int kLgQ = 256;                // queries per workgroup
@@ -68,17 +57,17 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
   const int q0 = qb * kLgQ + w * 32;
   const int half = lane >> 5;
 
-  // this wave's 32 queries as the B operand (lane: q = l&31, d = 16kd + 8(l>>5) + j): asm loads
+  // this wave's 32 queries as the B operand: asm loads
   // (hipcc cannot count a plain load against the LDS-DMA pieces behind it and would drain the
   // stream with vmcnt(0)), retired by the prologue's wait statement that names qf (form (ii) of
   // cdna_hip_programming.md §5.7 item 1; audited by tools/check_kernels.py)
   bf16x8 qf[4];
   {
-    const int qr = TAIL ? min(q0 + (lane & 31), S - 1) : q0 + (lane & 31);
-    const bf16_t* qp = base + (int64_t)qr * ld + 8 * half;
+    const int qr = TAIL ? min(q_frag_row(q0, lane), S - 1) : q_frag_row(q0, lane);
+    const bf16_t* qp = base + (int64_t)qr * ld;
 #pragma unroll
     for (int kd = 0; kd < 4; ++kd)
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[kd]) : "v"(qp + 16 * kd));
+      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[kd]) : "v"(q_frag_ptr(qp, kd, half)));
   }
   // chunk c -> stage c % 4: wave w loads piece w of the stage's 16 pieces (8 K pieces, then
   // 8 V pieces; a piece = 8 key rows x 128 B = 1 KiB) and piece w + 8
@@ -88,9 +77,9 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
 #pragma unroll
     for (int isV = 0; isV < 2; ++isV) {
       const int row = w * 8 + (lane >> 3);  // key row within the chunk
-      const int ch = (lane & 7) ^ (isV ? swzV(row) : swzK(row));
+      const int ch = stage_chunk(row, lane, isV);
       const int key = TAIL ? min(c * kLgChunk + row, S - 1) : c * kLgChunk + row;
-      const bf16_t* src = base + (int64_t)key * ld + (isV ? 2 * D : D) + ch * 8;
+      const bf16_t* src = stage_src(base, key, ld, D, isV, 0, ch);
       __builtin_amdgcn_global_load_lds(VP_GLB_PTR(src), VP_LDS_PTR(st + isV * kLgChunk * 128 + w * 1024),
                                        16, 0, 0);
     }
@@ -101,8 +90,7 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
   // chunk-0 wait is then a no-op
   asm volatile("s_waitcnt vmcnt(4)" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]) : : "memory");
 
-  const float c1 = 2.0f * kLog2e / cap;
-  const float c2 = cap * kLog2e;
+  const float c1 = cap_c1(cap), c2 = cap_c2(cap);
   f32x16 y0 = {}, y1 = {};
   [[maybe_unused]] f32x16 ysum = {};
   float lsum = 0.0f;
@@ -116,13 +104,14 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
     if (w >= 4) __builtin_amdgcn_s_setprio(1);  // static priority for the second-dispatched half
   }
 
-  // per-lane K / V read bases of the stage-unrolled loop (stage and key offsets are immediates there): krow = kt 32 + krow_l, so
-  // swzK(krow) = (krow_l >> 1) & 7 and, for key = kt 32 + 16 s + 4 half + trq, swzV(key) = ((trq >> 1) & 1) << 2
+  // per-lane K / V read bases of the stage-unrolled loop (stage and key offsets are immediates there): krow =
+  // kt 32 + krow_l, so swzK(krow) = swzK(krow_l) and, for key = kt 32 + 16 s + 4 half + trq, swzV(key) =
+  // ((trq >> 1) & 1) << 2 (V: attention_tile.h v_read_at at key row 4 half + trq, written out)
   [[maybe_unused]] uint32_t kb[4], vb[2];
   if constexpr ((VAR & 1024) == 0) {
     const uint32_t sb = (uint32_t)(uintptr_t)VP_LDS_PTR(smem);
 #pragma unroll
-    for (int kd = 0; kd < 4; ++kd) kb[kd] = sb + krow_l * 128 + (((2 * kd + half) ^ ((krow_l >> 1) & 7)) << 4);
+    for (int kd = 0; kd < 4; ++kd) kb[kd] = k_read_at(sb, krow_l, kd, half);
 #pragma unroll
     for (int dh = 0; dh < 2; ++dh) {
       const int col = 32 * dh + 16 * (g & 1) + 4 * trp;
@@ -157,10 +146,7 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
       } else {
         uint32_t kad[4];
 #pragma unroll
-        for (int kd = 0; kd < 4; ++kd) {
-          const int cc = 2 * kd + half;
-          kad[kd] = (uint32_t)(uintptr_t)VP_LDS_PTR(Ks + krow * 128 + ((cc ^ swzK(krow)) << 4));
-        }
+        for (int kd = 0; kd < 4; ++kd) kad[kd] = lds_addr(k_read_at(Ks, krow, kd, half));
         lds_read4_b128(kf, kad);
       }
 #pragma unroll
@@ -169,8 +155,7 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
       capped_exp16<(VAR & 1) == 0, (VAR & 2) == 0, (VAR & 8) == 0, (VAR & 64) != 0, (VAR & 128) != 0>(x, p, c1, c2,
                                                                                                      cp);
       if constexpr (TAIL) {
-        // keys past S (the last chunk only): weight 0.  Lane l, value i holds key row
-        // 8 (i / 4) + 4 (l / 32) + i % 4 of the 32-key tile (the 32x32 MFMA output layout)
+        // keys past S (the last chunk only): weight 0
         const int kbase = c * kLgChunk + kt * 32 + 4 * half;
         if (kbase + 28 >= S) {
 #pragma unroll
@@ -194,7 +179,7 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
 #pragma unroll
         for (int i = 0; i < 16; ++i) lsum += p[i];
       }
-      bf16x8 pf[2];
+      bf16x8 pf[2];  // (attention_tile.h pack_numerators, written out for VAR 32)
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         uint32_t u[4];
@@ -221,17 +206,13 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
         for (int s = 0; s < 2; ++s) {
           const int key = kt * 32 + 16 * s + 4 * half + trq;
 #pragma unroll
-          for (int dh = 0; dh < 2; ++dh) {
-            const int col = 32 * dh + 16 * (g & 1) + 4 * trp;
-            const int cc = col >> 3;
-            vad[s][dh] = (uint32_t)(uintptr_t)VP_LDS_PTR(Vs + key * 128 + ((cc ^ swzV(key)) << 4) + (col & 7) * 2);
-          }
+          for (int dh = 0; dh < 2; ++dh) vad[s][dh] = lds_addr(v_read_at(Vs, key, dh, lane));
         }
         lds_tr_read8(vr, vad);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
+      for (int s = 0; s < 2; ++s) {  // (attention_tile.h pv_mfma)
 #pragma unroll
         for (int dh = 0; dh < 2; ++dh) {
           const s16x4 lo = vr[s][dh][0], hi = vr[s][dh][1];
@@ -267,39 +248,31 @@ __global__ __launch_bounds__(kLgThreads, 4) void attn_long_kernel(const bf16_t* 
   bf16_t* op = o + ((int64_t)seq * S + q0 + (lane & 31)) * D + h * 64 + 4 * half;
 #pragma unroll
   for (int g4 = 0; g4 < 4; ++g4) {
-    uint2 v0 = make_uint2(pack_bf16x2(y0[4 * g4] * inv, y0[4 * g4 + 1] * inv),
-                          pack_bf16x2(y0[4 * g4 + 2] * inv, y0[4 * g4 + 3] * inv));
-    uint2 v1 = make_uint2(pack_bf16x2(y1[4 * g4] * inv, y1[4 * g4 + 1] * inv),
-                          pack_bf16x2(y1[4 * g4 + 2] * inv, y1[4 * g4 + 3] * inv));
+    const uint2 v0 = pack_o_quad(y0, g4, inv), v1 = pack_o_quad(y1, g4, inv);
     *reinterpret_cast<uint2*>(op + 8 * g4) = v0;
     *reinterpret_cast<uint2*>(op + 32 + 8 * g4) = v1;
   }
-}
-
-template <int VAR, bool TAIL>
-hipError_t launch_attn_long_t(const bf16_t* qkv, bf16_t* o, int num_seq, int S, int heads, float cap, hipStream_t s) {
-  const void* fn = reinterpret_cast<const void*>(attn_long_kernel<VAR, TAIL>);
-  hipError_t e = ensure_dyn_lds(fn, kLgLds);
-  if (e != hipSuccess) return e;
-  const int nqb = (S + kLgQ - 1) / kLgQ;
-  const int64_t grid = (int64_t)num_seq * heads * nqb;
-  if (grid > 0x7fffffff) return hipErrorInvalidValue;
-  const int xcd_map = grid % 8 == 0 ? 1 : 0;
-  const CapPoly cp = make_cap_poly(cap);
-  VP_NOTE_KERNEL(fn);
-  hipLaunchKernelGGL((attn_long_kernel<VAR, TAIL>), dim3((unsigned)grid), dim3(kLgThreads), kLgLds, s, qkv, o, S,
-                     heads, nqb, cap, xcd_map, cp);
-  return hipGetLastError();
 }
 
 // S % 256 == 0 (S >= 256) or any S > 256 (TAIL: the prologue's three chunks exist)
 template <int VAR>
 hipError_t launch_attn_long(const bf16_t* qkv, bf16_t* o, int num_seq, int S, int heads, float cap, hipStream_t s) {
   if (S < kLgQ || !(cap > 0.0f) || num_seq < 1) return hipErrorInvalidValue;
-  if (S % kLgQ == 0) return launch_attn_long_t<VAR, false>(qkv, o, num_seq, S, heads, cap, s);
-  return launch_attn_long_t<VAR, true>(qkv, o, num_seq, S, heads, cap, s);
+  return with_bool(S % kLgQ != 0, [&](auto tail) {
+    const auto kernel = attn_long_kernel<VAR, decltype(tail)::value>;
+    hipError_t e = ensure_dyn_lds((const void*)kernel, kLgLds);
+    if (e != hipSuccess) return e;
+    const int nqb = (S + kLgQ - 1) / kLgQ;
+    const int64_t grid = (int64_t)num_seq * heads * nqb;
+    if (grid > 0x7fffffff) return hipErrorInvalidValue;
+    const int xcd_map = grid % 8 == 0 ? 1 : 0;
+    const CapPoly cp = make_cap_poly(cap);
+    VP_NOTE_KERNEL(kernel);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kLgThreads), kLgLds, s, qkv, o, S, heads, nqb, cap, xcd_map,
+                       cp);
+    return hipGetLastError();
+  });
 }
-
 
 }  // namespace
 

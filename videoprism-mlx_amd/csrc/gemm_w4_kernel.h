@@ -56,13 +56,6 @@ __device__ __forceinline__ int swz(int row) { return (row >> 1) & 7; }
 
 __device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 
-typedef short w4_s16x4 __attribute__((ext_vector_type(4)));
-// 4 bf16 of one LDS column (rows +0..3 of 16-bit element p) as an MFMA operand
-__device__ __forceinline__ bf16x4 w4_tr_read(const char* p) {
-  const w4_s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) w4_s16x4*)(p));
-  return bf16x4{v[0], v[1], v[2], v[3]};
-}
-
 // NOPAD: the launch has no padded rows (rowpad == nullptr), so the (1 - rowpad) factor is skipped --
 // bitwise the same result (ffn_layer1: 651.7 -> 639.5 us; the same build of the residual epilogues
 // measured slower in the forward, a different compiler schedule, so only ffn_layer1 uses it).
@@ -656,7 +649,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
           const char* vb = scr + (st & 1) * 2048;
           bf16x4 vf[4];
 #pragma unroll
-          for (int dt = 0; dt < 4; ++dt) vf[dt] = w4_tr_read(vb + vunit(4 * g4 + trq, 4 * dt + trp));
+          for (int dt = 0; dt < 4; ++dt) vf[dt] = tr_read(vb + vunit(4 * g4 + trq, 4 * dt + trp));
           if (st + 1 < 16) {
             if (st + 1 == 8) ld_consts(1);
             fold_write(st + 1);

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 
 namespace vp {
@@ -240,6 +241,13 @@ __device__ __forceinline__ void wait_vmcnt0() { asm volatile("s_waitcnt vmcnt(0)
 // destination that does not carry its wait in the same statement. ----
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
+// one compiler-visible transposed read (a builtin, not an asm load: for kernels with no LDS-DMA in flight): 4 bf16 of
+// one LDS column (rows +0..3 of 16-bit element p) as an MFMA operand
+__device__ __forceinline__ bf16x4 tr_read(const char* p) {
+  const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+  return bf16x4{v[0], v[1], v[2], v[3]};
+}
+
 // 8 transposed reads (ds_read_b64_tr_b16) at ad[s][dh] and ad[s][dh] + 1024 -> v[s][dh][0 / 1]
 __device__ __forceinline__ void lds_tr_read8(s16x4 (&v)[2][2][2], const uint32_t (&ad)[2][2]) {
   asm volatile(
@@ -302,6 +310,16 @@ __device__ __forceinline__ void lds_tr_read8_o(s16x4 (&v)[2][2][2], const uint32
         "=&v"(v[1][0][1]), "=&v"(v[1][1][0]), "=&v"(v[1][1][1])
       : "v"(ad[0]), "v"(ad[1]), "n"(OFF), "n"(OFF + 1024), "n"(OFF + 2048), "n"(OFF + 3072)
       : "memory");
+}
+
+// ---- launch helpers (host) ----
+// a run-time flag as a compile-time one: f(std::true_type{}) or f(std::false_type{}); nested for two flags, so a
+// launcher names its bool-templated kernel instantiation once.  (The false branch stands first so the <false, ...>
+// instantiations come first in the device listing, as they always did: the assembly audit's tests open the first
+// kernel of attention.s.)
+template <class F>
+auto with_bool(bool b, F&& f) {
+  return !b ? f(std::false_type{}) : f(std::true_type{});
 }
 
 // ---- per-device launch state (host) ----

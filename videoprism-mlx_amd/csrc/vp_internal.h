@@ -15,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "attention_tile.h"
 #include "vp_kernels.h"
 #include "vp_params.h"
 
@@ -531,11 +532,12 @@ inline hipError_t launch_attention(int kind, bool bf16, const void* qkv, void* o
 }
 
 // the fused temporal attention's cap arguments (EPI_*_TATTN_LN): cap_c1 / cap_c2 are the capped-exp constants
-// 2 log2(e) / cap and cap log2(e), the same IEEE division the unfused kernels do on the device
+// 2 log2(e) / cap and cap log2(e), the same IEEE division the unfused kernels do on the device: the one expression
+// both evaluate (attention_tile.h cap_c1 / cap_c2)
 inline void set_tattn_cap(vp::EpiArgs& ep, float cap, int heads) {
   ep.cap = cap; ep.heads = heads;
-  ep.cap_c1 = 2.0f * 1.4426950408889634f / cap;
-  ep.cap_c2 = cap * 1.4426950408889634f;
+  ep.cap_c1 = vp::cap_c1(cap);
+  ep.cap_c2 = vp::cap_c2(cap);
 }
 
 // The fp32 GEMM sums each output in one k-ordered chain, whose rounding error grows as sqrt(K): at Base's and
