@@ -118,6 +118,42 @@ int vp_forward(vp_handle* h, const void* video, int in_dtype, int64_t B, int64_t
                int64_t W, const float* frame_paddings, void* out, int out_dtype,
                void* spatial_out, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---------------- sliding windows: per-frame spatial states, computed once ----------------
+ * FactorizedEncoder is factorized: the spatial layers see one frame at a time (encoders.py:459-478) and a frame
+ * first meets its neighbours in the transpose to (b n) t (:535).  Overlapping windows of one long video therefore
+ * share the spatial half: vp_forward_spatial runs it once per frame, vp_forward_temporal runs the rest over any
+ * windows of those frames.  Neither allocates or synchronises.
+ *
+ * A frame state is the spatial residual stream after the last spatial layer, *before* spatial_ln: [F][N][D] in the
+ * handle's fprop dtype, rows (frame, patch).  It depends on its frame's pixels and padding only: not on F, on the
+ * frame's place in the batch, or on any T.  vp_forward_temporal copies the windows' frames out of the states (one
+ * launch) and from there runs vp_forward's own launches, the fused spatial_ln + transpose + temporal pos-emb
+ * included, which makes its outputs bitwise those of vp_forward on the gathered clips.
+ *
+ * vp_forward_spatial replaces encoders.py:436-514 and :459-478 (tokenisation, patch projection, spatial pos-emb,
+ * spatial encoder) over F frames, exactly as vp_forward does for B = F, T = 1:
+ *   video          device [F, H, W, 3], in_dtype VP_F32, VP_BF16 or VP_U8
+ *   frame_paddings device [F] fp32 (1 = padded frame) or NULL
+ *   states_out     device [F, N, D] in the fprop dtype */
+int vp_spatial_workspace_bytes(const vp_handle* h, int64_t F, int64_t H, int64_t W, size_t* bytes);
+int vp_forward_spatial(vp_handle* h, const void* video, int in_dtype, int64_t F, int64_t H, int64_t W,
+                       const float* frame_paddings, void* states_out, void* workspace, size_t ws_bytes,
+                       void* stream);
+/* vp_forward_temporal replaces encoders.py:520-578 (spatial_ln, transpose, temporal pos-emb, temporal encoder,
+ * temporal_ln) over Wn windows of T frames each:
+ *   states         device [F, N, D] frame states in the fprop dtype (vp_forward_spatial)
+ *   frame_idx      device int32 [Wn, T]: window w's frame t is state frame_idx[w][t].  The gather kernel clamps each
+ *                  index to [0, F - 1]: an index out of range is the caller's error, but no read leaves `states`
+ *   frame_paddings device [Wn, T] fp32 (the frames' paddings, gathered by the caller) or NULL
+ *   out            device [Wn, T*N, D] embeddings in out_dtype
+ *   spatial_out    device [Wn, T*N, D] 'spatial_features' in out_dtype, or NULL
+ * A T without a temporal table gives VP_ESTATE (vp_prepare_frames), as in vp_forward.  Windows are processed in
+ * chunks as vp_forward's clips are. */
+int vp_temporal_workspace_bytes(const vp_handle* h, int64_t Wn, int64_t T, int64_t H, int64_t W, size_t* bytes);
+int vp_forward_temporal(vp_handle* h, const void* states, int64_t F, const int32_t* frame_idx, int64_t Wn,
+                        int64_t T, int64_t H, int64_t W, const float* frame_paddings, void* out, int out_dtype,
+                        void* spatial_out, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---------------- HIP-event profiler (bench.py's live per-kernel timing) ----------------
  * vp_profile_enable(h, n): the next n kernel launches of vp_forward are bracketed by
  * hipEventRecord on the launch stream (0 disables).  vp_profile_read syncs on the last event
@@ -273,6 +309,17 @@ int vp_clip_encode_video(vp_clip* c, const void* video, int in_dtype, int64_t B,
                          void* spatiotemporal_out, int out_dtype, void* workspace,
                          size_t ws_bytes, void* stream);
 
+/* vp_clip_encode_video over Wn windows of T frames of the vision tower's frame states (vp_forward_spatial on
+ * vp_clip_video_handle; states, F, frame_idx and frame_paddings as in vp_forward_temporal): the vision features
+ * (encoders.py:833-845) come from vp_forward_temporal, everything after them is vp_clip_encode_video's.  Outputs
+ * are indexed by window where vp_clip_encode_video's are by clip. */
+int vp_clip_video_windows_workspace_bytes(const vp_clip* c, int64_t Wn, int64_t T, int64_t H, int64_t W,
+                                          size_t* bytes);
+int vp_clip_encode_video_windows(vp_clip* c, const void* states, int64_t F, const int32_t* frame_idx, int64_t Wn,
+                                 int64_t T, int64_t H, int64_t W, const float* frame_paddings, int normalize,
+                                 float* video_emb, float* frame_emb, void* spatial_out, void* spatiotemporal_out,
+                                 int out_dtype, void* workspace, size_t ws_bytes, void* stream);
+
 /* Text side (encoders.py:887-908): ids device int32 [Q, L], paddings device fp32 [Q, L]
  * (1 = padded token); text_emb device [Q, D] fp32 = the CLS token after unimodal_ln,
  * L2-normalised if `normalize`.  Out-of-range ids are clamped (JAX gather semantics). */
@@ -305,6 +352,16 @@ int vp_classifier_forward(vp_classifier* c, const void* video, int in_dtype, int
                           int64_t H, int64_t W, const float* frame_paddings, float* logits,
                           float* embeddings, void* spatial_out, void* spatiotemporal_out,
                           int out_dtype, void* workspace, size_t ws_bytes, void* stream);
+
+/* vp_classifier_forward over Wn windows of T frames of the encoder's frame states (vp_forward_spatial on
+ * vp_classifier_video_handle; arguments as in vp_forward_temporal): the features of encoders.py:621-630 come from
+ * vp_forward_temporal, the pooler and projection are vp_classifier_forward's. */
+int vp_classifier_windows_workspace_bytes(const vp_classifier* c, int64_t Wn, int64_t T, int64_t H, int64_t W,
+                                          size_t* bytes);
+int vp_classifier_forward_windows(vp_classifier* c, const void* states, int64_t F, const int32_t* frame_idx,
+                                  int64_t Wn, int64_t T, int64_t H, int64_t W, const float* frame_paddings,
+                                  float* logits, float* embeddings, void* spatial_out, void* spatiotemporal_out,
+                                  int out_dtype, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---------------- multi-GPU: RCCL all-gather of pooled clip embeddings ----------------
  * The reference runs on one device; its video-text usage scores every clip against every query,

@@ -495,6 +495,27 @@ __global__ __launch_bounds__(256) void expand_paddings_kernel(const float* __res
   }
 }
 
+// ---- frame gather (sliding windows over per-frame states, vp_kernels.h gather_frames) ----
+// Slot s = blockIdx.x of the windows' (w, t) slots takes frame clamp(frame_idx[s], 0, nframes - 1) of x: frames of
+// frame_vec 16-byte vectors, blockIdx.y walking a frame in pieces of 256 x 4 vectors.  The index is one uniform load
+// ahead of the copies, a thread's 4 loads are issued before its first store, and the clamp keeps every read inside x
+// whatever the indices hold.
+__global__ __launch_bounds__(256) void gather_frames_kernel(const uint4* __restrict__ x,
+                                                            const int32_t* __restrict__ frame_idx, int nframes,
+                                                            int64_t frame_vec, uint4* __restrict__ out) {
+  const int raw = frame_idx[blockIdx.x];
+  const int f = raw < 0 ? 0 : raw > nframes - 1 ? nframes - 1 : raw;
+  const uint4* src = x + (int64_t)f * frame_vec;
+  uint4* dst = out + (int64_t)blockIdx.x * frame_vec;
+  const int64_t i0 = (int64_t)blockIdx.y * 1024 + threadIdx.x;
+  uint4 v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (i0 + j * 256 < frame_vec) v[j] = src[i0 + j * 256];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (i0 + j * 256 < frame_vec) dst[i0 + j * 256] = v[j];
+}
 
 // ---- pooled clip embedding: out[b] = l2norm(mean_l emb[b, l, :]) (encoders.py:50-67) ----
 template <typename T>
@@ -689,6 +710,18 @@ hipError_t expand_paddings(const float* frame_pad, int B, int T, int Nsp, float*
                            float* pad_bnt, hipStream_t s) {
   hipLaunchKernelGGL(expand_paddings_kernel, dim3(grid_for((int64_t)B * T * Nsp, 256)), dim3(256),
                      0, s, frame_pad, B, T, Nsp, pad_btn, pad_bnt);
+  return hipGetLastError();
+}
+
+hipError_t gather_frames(const void* x, int64_t nframes, const int32_t* frame_idx, int64_t nslots, int64_t frame_bytes,
+                         void* out, hipStream_t s) {
+  const int64_t frame_vec = frame_bytes / 16, pieces = (frame_vec + 1023) / 1024;
+  if (!x || !frame_idx || !out || nframes < 1 || nframes > 0x7fffffff || nslots < 1 || nslots > 0x7fffffff ||
+      frame_bytes < 16 || frame_bytes % 16 || pieces > 65535 || ((uintptr_t)x & 15) || ((uintptr_t)out & 15))
+    return hipErrorInvalidValue;
+  VP_NOTE_KERNEL(gather_frames_kernel);
+  hipLaunchKernelGGL(gather_frames_kernel, dim3((unsigned)nslots, (unsigned)pieces), dim3(256), 0, s,
+                     static_cast<const uint4*>(x), frame_idx, (int)nframes, frame_vec, static_cast<uint4*>(out));
   return hipGetLastError();
 }
 

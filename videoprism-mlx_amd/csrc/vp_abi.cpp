@@ -264,15 +264,50 @@ int vp_workspace_bytes(const vp_handle* h, int64_t B, int64_t T, int64_t H, int6
 
 namespace {
 
-// FactorizedEncoder.__call__ over one chunk of B clips (B <= chunk_clips: a workspace of about 4 GiB of
-// FFN hidden activation); vp_forward below walks the batch chunk by chunk
-int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int64_t T, int64_t H,
-                  int64_t W, const float* frame_paddings, void* out, int out_dtype,
-                  void* spatial_out, void* workspace, void* stream) {
-  using namespace vp;
-  int rc;
-  const WsLayout L = ws_layout(h, B, T, H, W);
+// What the two halves of a forward chunk share: the workspace carve-up for B x T frames of H x W, the launch
+// context and the token paddings in both row orders.
+struct Chunk {
+  WsLayout L;
+  hipStream_t s = nullptr;
+  bool bf = false;
+  int Nsp = 0, M = 0, Mp = 0;  // patches per frame, tokens, GEMM rows
+  char* ws = nullptr;
+  float* pad_btn = nullptr;
+  float* pad_bnt = nullptr;
+  Fwd f;
+};
 
+// the spatial positional table for frames of H x W (encoders.py:497-512)
+int find_spatial_pos(const vp_handle* h, int64_t H, int64_t W, const float** sp_pos) {
+  const vp_config& c = h->cfg;
+  const int P_ = c.patch_size;
+  const int Nsp = (int)((H / P_) * (W / P_));
+  *sp_pos = h->spatial_pos;
+  if (Nsp != c.pos_emb_h * c.pos_emb_w || H / P_ != c.pos_emb_h) {
+    auto it = h->grid_pos.find({(int)(H / P_), (int)(W / P_)});
+    if (it == h->grid_pos.end())
+      return fail(VP_ESTATE, "patch grid differs from pos_emb_shape[1:]: call vp_prepare_geometry first");
+    *sp_pos = it->second;
+  }
+  return VP_OK;
+}
+
+// the temporal positional table for clips of T frames (encoders.py:543-553)
+int find_temporal_pos(const vp_handle* h, int64_t T, const float** tpos) {
+  const auto tp = h->temporal_pos.find((int)T);
+  if (tp == h->temporal_pos.end())
+    return fail(VP_ESTATE, "no temporal positional table for T = " + std::to_string(T) + ": call vp_prepare_frames first");
+  *tpos = tp->second;
+  return VP_OK;
+}
+
+// Opens a chunk of B x T frames in `workspace`: sets the device, expands the frame paddings [B*T] to token paddings
+// and fills the launch context.  The first launches of a forward chunk.
+int begin_chunk(vp_handle* h, int64_t B, int64_t T, int64_t H, int64_t W, const float* frame_paddings,
+                void* workspace, void* stream, Chunk* ck) {
+  using namespace vp;
+  ck->L = ws_layout(h, B, T, H, W);
+  const WsLayout& L = ck->L;
   VP_HIP(hipSetDevice(h->device));
   hipStream_t s = static_cast<hipStream_t>(stream);
   const vp_config& c = h->cfg;
@@ -281,49 +316,51 @@ int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int6
   const int Nsp = (int)((H / P_) * (W / P_));
   const int M = (int)(B * T * Nsp);  // tokens
   const int Mp = (int)padded_rows(h, M);  // GEMM rows
-  const float* sp_pos = h->spatial_pos;
-  if (Nsp != c.pos_emb_h * c.pos_emb_w || H / P_ != c.pos_emb_h) {  // encoders.py:497-512
-    auto it = h->grid_pos.find({(int)(H / P_), (int)(W / P_)});
-    if (it == h->grid_pos.end())
-      return fail(VP_ESTATE, "patch grid differs from pos_emb_shape[1:]: call vp_prepare_geometry first");
-    sp_pos = it->second;
-  }
-  const auto tp = h->temporal_pos.find((int)T);
-  if (tp == h->temporal_pos.end())
-    return fail(VP_ESTATE, "no temporal positional table for T = " + std::to_string(T) + ": call vp_prepare_frames first");
-  const float* tpos = tp->second;
-  const int D = c.model_dim, F = c.mlp_dim, NH = c.num_heads;
-  const size_t es = bf ? 2 : 4;
+  const int D = c.model_dim;
   char* ws = static_cast<char*>(workspace);
-  void* x = ws + L.x;
-  void* x2 = ws + L.x2;
-  void* hb = ws + L.hbuf;
-  void* big = ws + L.big;
-  float* pad_btn = nullptr;
-  float* pad_bnt = nullptr;
+  ck->s = s; ck->bf = bf; ck->Nsp = Nsp; ck->M = M; ck->Mp = Mp; ck->ws = ws;
+  const char* ge = bf ? gemm_bf16_check(Mp, 3 * D, D, D, D) : gemm_f32_check(Mp, 3 * D, D, D, D);
+  if (ge) return fail(VP_ENOTSUP, ge);
   if (frame_paddings) {
-    pad_btn = reinterpret_cast<float*>(ws + L.pad_btn);
-    pad_bnt = reinterpret_cast<float*>(ws + L.pad_bnt);
+    float* pad_btn = reinterpret_cast<float*>(ws + L.pad_btn);
+    float* pad_bnt = reinterpret_cast<float*>(ws + L.pad_bnt);
     if (Mp > M) {
       VP_HIP(hipMemsetAsync(pad_btn + M, 0, (size_t)(Mp - M) * 4, s));
       VP_HIP(hipMemsetAsync(pad_bnt + M, 0, (size_t)(Mp - M) * 4, s));
     }
     VP_HIP(expand_paddings(frame_paddings, (int)B, (int)T, Nsp, pad_btn, pad_bnt, s));
+    ck->pad_btn = pad_btn;
+    ck->pad_bnt = pad_bnt;
   }
   // bf16: LayerNorms inside the layers are folded into the consuming GEMMs (EPI_*_LN); the
   // residual-stream producers emit row statistics (EPI_*_ST) that ln_stats_finalize turns into
   // (rstd, -mean*rstd) per row
-  Fwd f;
-  f.s = s; f.bf = bf; f.M = Mp; f.D = D; f.NH = NH; f.cap = c.atten_logit_cap;
-  f.hb = hb; f.big = big;
+  Fwd& f = ck->f;
+  f.s = s; f.bf = bf; f.M = Mp; f.D = D; f.NH = c.num_heads; f.cap = c.atten_logit_cap;
+  f.hb = ws + L.hbuf; f.big = ws + L.big;
   f.f32_two_chains = f32_two_chains(c);
   f.st_part = reinterpret_cast<float*>(ws + L.st_part);
   f.ln_rs = reinterpret_cast<float*>(ws + L.ln_rs);
   f.pf = &h->prof;
-  float* ln_rs = f.ln_rs;
+  return VP_OK;
+}
+
+// The spatial half of FactorizedEncoder.__call__ (encoders.py:436-514, :459-478) over the BT frames of an open chunk:
+// leaves the spatial residual stream, before spatial_ln, in x [Mp][D] (the frame states)
+int spatial_half(vp_handle* h, Chunk& ck, const void* video, int in_dtype, int64_t BT, int64_t H, int64_t W,
+                 const float* sp_pos, void* x) {
+  using namespace vp;
+  int rc;
+  hipStream_t s = ck.s;
+  const vp_config& c = h->cfg;
+  const bool bf = ck.bf;
+  const int P_ = c.patch_size;
+  const int Nsp = ck.Nsp, M = ck.M, Mp = ck.Mp;
+  const int D = c.model_dim, F = c.mlp_dim;
+  const size_t es = bf ? 2 : 4;
+  Fwd& f = ck.f;
+  void* big = f.big;
   const int epi_pos = bf ? EPI_POS_BF16 : EPI_POS_F32;
-  const char* ge = bf ? gemm_bf16_check(Mp, 3 * D, D, D, D) : gemm_f32_check(Mp, 3 * D, D, D, D);
-  if (ge) return fail(VP_ENOTSUP, ge);
   const double dM = M, dD = D, dE = (double)es;
   auto gbytes = [&](double K, double N, double outb, double resid) { return gemm_bytes(dM, K, N, dE, outb, resid); };
 
@@ -341,7 +378,7 @@ int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int6
     const bf16_t* frames = static_cast<const bf16_t*>(video);
     if (in_dtype != VP_BF16) {
       VP_HIP(f.rec(PC_PATCHIFY, 0.0, dM * kreal * (in_es + dE), [&] {
-        return video_to_bf16(video, in_dtype, static_cast<bf16_t*>(big), (int64_t)B * T * H * W * 3, s); }));
+        return video_to_bf16(video, in_dtype, static_cast<bf16_t*>(big), (int64_t)BT * H * W * 3, s); }));
       frames = static_cast<const bf16_t*>(big);
     }
     EpiArgs ep = epi_args(x, D, h->bpatch, nullptr, 0, sp_pos, Nsp, nullptr);
@@ -353,34 +390,103 @@ int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int6
     if (Mp > M) VP_HIP(hipMemsetAsync(static_cast<char*>(big) + (size_t)M * h->kpad * es, 0,
                                       (size_t)(Mp - M) * h->kpad * es, s));
     VP_HIP(f.rec(PC_PATCHIFY, 0.0, dM * kreal * in_es + dM * h->kpad * dE, [&] {
-      return patchify(video, in_dtype, big, bf, (int)(B * T), (int)H, (int)W, 3, P_, h->kpad, s); }));
+      return patchify(video, in_dtype, big, bf, (int)BT, (int)H, (int)W, 3, P_, h->kpad, s); }));
     VP_HIP(f.rec(PC_GEMM_PATCH, 2.0 * dM * kreal * dD, gbytes(kreal, dD, dE, 0), [&] {
       return f.gemm(fold ? EPI_POS_BF16_ST : epi_pos, big, h->kpad, h->wpatch, D, x, D, h->bpatch, nullptr,
                     sp_pos, Nsp, nullptr); }));
   }
-  const double ln_bytes = dM * dD * dE + dM * dD * dE;
   if (fold) VP_HIP(f.finalize());
-  auto run_stack = [&](std::vector<LayerW>& layers, void* xs, int num_seq, int S, const float* pad) -> int {
-    const int acls = num_seq == (int)(B * T) ? PC_ATTN_SPATIAL : PC_ATTN_TEMPORAL;
-    return f.run_stack(layers, xs, num_seq, S, pad, F, acls, ATT_VIDEO, bf, false);
-  };
-  auto rec = [&](int cls, double flops, double bytes, auto&& fn) { return f.rec(cls, flops, bytes, fn); };
   // 2. spatial encoder over (b t) sequences of Nsp tokens
-  if ((rc = run_stack(h->spatial, x, (int)(B * T), Nsp, pad_btn))) return rc;
+  if ((rc = f.run_stack(h->spatial, x, (int)BT, Nsp, ck.pad_btn, F, PC_ATTN_SPATIAL, ATT_VIDEO, bf, false))) return rc;
+  return VP_OK;
+}
+
+// The temporal half (encoders.py:520-578) over the B clips of T frames of an open chunk.  frame_idx == nullptr
+// (vp_forward): x is the chunk's own residual stream [B*T*Nsp][D], rows in place.  Else x holds the states of nframes frames and clip b's
+// frame t is frame frame_idx[b*T + t] of them: one copy launch (gather_frames, vp_kernels.h) puts them into the
+// chunk's residual stream, and from there on the launches are the same, kernel for kernel, which is what makes a
+// window's output bitwise vp_forward's on the gathered clip.  (A LayerNorm that gathers as it loads would save that
+// pass, but it is another kernel than layernorm's, and the compiler contracts multiplies and adds differently in the
+// two: their outputs differ in the last bit of a few values.)
+int temporal_half(vp_handle* h, Chunk& ck, const void* x, const int32_t* frame_idx, int64_t nframes, int64_t B,
+                  int64_t T, const float* tpos, void* out, int out_dtype, void* spatial_out) {
+  using namespace vp;
+  int rc;
+  hipStream_t s = ck.s;
+  const vp_config& c = h->cfg;
+  const bool bf = ck.bf;
+  const int Nsp = ck.Nsp, M = ck.M;
+  const int D = c.model_dim, F = c.mlp_dim;
+  const size_t es = bf ? 2 : 4;
+  Fwd& f = ck.f;
+  void* x2 = ck.ws + ck.L.x2;
+  float* ln_rs = bf && c.num_temporal_layers > 0 ? f.ln_rs : nullptr;
+  const double dM = M, dD = D, dE = (double)es;
+  const double ln_bytes = dM * dD * dE + dM * dD * dE;
+  auto rec = [&](int cls, double flops, double bytes, auto&& fn) { return f.rec(cls, flops, bytes, fn); };
+  if (frame_idx) {
+    void* xg = ck.ws + ck.L.x;
+    VP_HIP(rec(PC_MISC, 0.0, ln_bytes, [&] {
+      return gather_frames(x, nframes, frame_idx, B * T, (int64_t)Nsp * D * (int64_t)es, xg, s); }));
+    x = xg;
+  }
   // 3. spatial_ln (+ optional spatial_features), transpose to (b n) t, + temporal pos-emb
   if (spatial_out)
     VP_HIP(rec(PC_LAYERNORM, 0.0, dM * dD * dE + dM * dD * (double)dtype_bytes(out_dtype), [&] {
       return layernorm(x, bf, M, D, h->sln_g, h->sln_b, spatial_out, out_dtype == VP_BF16, PERM_NONE, 1, 1, nullptr, s); }));
   VP_HIP(rec(PC_LAYERNORM, 0.0, ln_bytes, [&] {
-    return layernorm(x, bf, M, D, h->sln_g, h->sln_b, x2, bf, PERM_BTN_TO_BNT, (int)T, Nsp, tpos, s,
-                     bf && c.num_temporal_layers > 0 ? ln_rs : nullptr); }));
+    return layernorm(x, bf, M, D, h->sln_g, h->sln_b, x2, bf, PERM_BTN_TO_BNT, (int)T, Nsp, tpos, s, ln_rs); }));
   // 4. temporal encoder over (b n) sequences of T tokens
-  if ((rc = run_stack(h->temporal, x2, (int)(B * Nsp), (int)T, pad_bnt))) return rc;
+  if ((rc = f.run_stack(h->temporal, x2, (int)(B * Nsp), (int)T, ck.pad_bnt, F, PC_ATTN_TEMPORAL, ATT_VIDEO, bf, false)))
+    return rc;
   // 5. temporal_ln and '(bn)td->b(tn)d'
   VP_HIP(rec(PC_LAYERNORM, 0.0, dM * dD * dE + dM * dD * (double)dtype_bytes(out_dtype), [&] {
     return layernorm(x2, bf, M, D, h->tln_g, h->tln_b, out, out_dtype == VP_BF16, PERM_BNT_TO_BTN, (int)T, Nsp, nullptr, s); }));
-  (void)es;
   return VP_OK;
+}
+
+// FactorizedEncoder.__call__ over one chunk of B clips (B <= chunk_clips: a workspace of about 4 GiB of
+// FFN hidden activation); vp_forward below walks the batch chunk by chunk
+int forward_chunk(vp_handle* h, const void* video, int in_dtype, int64_t B, int64_t T, int64_t H,
+                  int64_t W, const float* frame_paddings, void* out, int out_dtype,
+                  void* spatial_out, void* workspace, void* stream) {
+  const float *sp_pos, *tpos;
+  int rc;
+  if ((rc = find_spatial_pos(h, H, W, &sp_pos)) || (rc = find_temporal_pos(h, T, &tpos))) return rc;
+  Chunk ck;
+  if ((rc = begin_chunk(h, B, T, H, W, frame_paddings, workspace, stream, &ck))) return rc;
+  void* x = ck.ws + ck.L.x;
+  if ((rc = spatial_half(h, ck, video, in_dtype, B * T, H, W, sp_pos, x))) return rc;
+  return temporal_half(h, ck, x, nullptr, 0, B, T, tpos, out, out_dtype, spatial_out);
+}
+
+// vp_forward_spatial over one chunk of F frames: the chunk B = F, T = 1 of forward_chunk, stopped before spatial_ln
+int spatial_chunk(vp_handle* h, const void* video, int in_dtype, int64_t F, int64_t H, int64_t W,
+                  const float* frame_paddings, void* states_out, void* workspace, void* stream) {
+  const float* sp_pos;
+  int rc;
+  if ((rc = find_spatial_pos(h, H, W, &sp_pos))) return rc;
+  Chunk ck;
+  if ((rc = begin_chunk(h, F, 1, H, W, frame_paddings, workspace, stream, &ck))) return rc;
+  // F*N a multiple of the GEMM row tile: the residual stream lives in states_out from the patch embedding on
+  const bool in_place = ck.Mp == ck.M;
+  void* x = in_place ? states_out : ck.ws + ck.L.x;
+  if ((rc = spatial_half(h, ck, video, in_dtype, F, H, W, sp_pos, x))) return rc;
+  if (!in_place)
+    VP_HIP(hipMemcpyAsync(states_out, x, (size_t)ck.M * h->cfg.model_dim * (ck.bf ? 2 : 4), hipMemcpyDeviceToDevice, ck.s));
+  return VP_OK;
+}
+
+// vp_forward_temporal over one chunk of Wn windows
+int temporal_chunk(vp_handle* h, const void* states, int64_t F, const int32_t* frame_idx, int64_t Wn, int64_t T,
+                   int64_t H, int64_t W, const float* frame_paddings, void* out, int out_dtype, void* spatial_out,
+                   void* workspace, void* stream) {
+  const float* tpos;
+  int rc;
+  if ((rc = find_temporal_pos(h, T, &tpos))) return rc;
+  Chunk ck;
+  if ((rc = begin_chunk(h, Wn, T, H, W, frame_paddings, workspace, stream, &ck))) return rc;
+  return temporal_half(h, ck, states, frame_idx, F, Wn, T, tpos, out, out_dtype, spatial_out);
 }
 
 }  // namespace
@@ -401,6 +507,51 @@ int vp_forward(vp_handle* h, const void* video, int in_dtype, int64_t B, int64_t
   return for_each_chunk(h, B, T, H, W, [&](int64_t b0, int64_t nb) {
     return forward_chunk(h, advance(video, b0 * in_clip), in_dtype, nb, T, H, W, advance(frame_paddings, b0 * T * 4),
                          advance(out, b0 * out_clip), out_dtype, advance(spatial_out, b0 * out_clip), workspace, stream);
+  });
+}
+
+int vp_spatial_workspace_bytes(const vp_handle* h, int64_t F, int64_t H, int64_t W, size_t* bytes) {
+  return vp_workspace_bytes(h, F, 1, H, W, bytes);
+}
+
+int vp_forward_spatial(vp_handle* h, const void* video, int in_dtype, int64_t F, int64_t H, int64_t W,
+                       const float* frame_paddings, void* states_out, void* workspace, size_t ws_bytes,
+                       void* stream) {
+  if (!h || !video || !states_out || !workspace) return fail(VP_EINVAL, "null argument");
+  if (!h->finalized) return fail(VP_ESTATE, "vp_finalize has not been called");
+  size_t need = 0, st_frame = 0;
+  const int fd = h->cfg.fprop_dtype;
+  int rc = check_dtypes(in_dtype, fd, false, fd);
+  if (rc || (rc = vp_spatial_workspace_bytes(h, F, H, W, &need)) ||
+      (rc = check_workspace(h, 1, H, W, ws_bytes, need, fd, &st_frame)))
+    return rc;
+  const size_t in_frame = video_clip_bytes(1, H, W, in_dtype);
+  return for_each_chunk(h, F, 1, H, W, [&](int64_t f0, int64_t nf) {
+    return spatial_chunk(h, advance(video, f0 * in_frame), in_dtype, nf, H, W, advance(frame_paddings, f0 * 4),
+                         advance(states_out, f0 * st_frame), workspace, stream);
+  });
+}
+
+int vp_temporal_workspace_bytes(const vp_handle* h, int64_t Wn, int64_t T, int64_t H, int64_t W, size_t* bytes) {
+  return vp_workspace_bytes(h, Wn, T, H, W, bytes);
+}
+
+int vp_forward_temporal(vp_handle* h, const void* states, int64_t F, const int32_t* frame_idx, int64_t Wn,
+                        int64_t T, int64_t H, int64_t W, const float* frame_paddings, void* out, int out_dtype,
+                        void* spatial_out, void* workspace, size_t ws_bytes, void* stream) {
+  if (!h || !states || !frame_idx || !out || !workspace) return fail(VP_EINVAL, "null argument");
+  if (!h->finalized) return fail(VP_ESTATE, "vp_finalize has not been called");
+  size_t need = 0, out_clip = 0;
+  int rc = check_dtypes(h->cfg.fprop_dtype, out_dtype, false, h->cfg.fprop_dtype);
+  if (rc || (rc = vp_temporal_workspace_bytes(h, Wn, T, H, W, &need)) ||
+      (rc = check_workspace(h, T, H, W, ws_bytes, need, out_dtype, &out_clip)))
+    return rc;
+  const int64_t P = h->cfg.patch_size;
+  if (F < 1 || F * (H / P) * (W / P) > 0x7fffffff)
+    return fail(VP_EINVAL, "states must hold 1 <= F frames and fewer than 2^31 rows");
+  return for_each_chunk(h, Wn, T, H, W, [&](int64_t w0, int64_t nw) {
+    return temporal_chunk(h, states, F, frame_idx + w0 * T, nw, T, H, W, advance(frame_paddings, w0 * T * 4),
+                          advance(out, w0 * out_clip), out_dtype, advance(spatial_out, w0 * out_clip), workspace, stream);
   });
 }
 
@@ -679,6 +830,44 @@ int vp_op_layernorm(const void* x, int in_dtype, int64_t rows, int64_t D, const 
   if (perm && (T < 1 || Nsp < 1 || rows % (T * Nsp))) return fail(VP_EINVAL, "bad permutation geometry");
   hipError_t e = layernorm(x, in_dtype == VP_BF16, (int)rows, (int)D, gamma, beta, out, out_dtype == VP_BF16,
                            perm, (int)T, (int)Nsp, add, static_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) return fail(VP_ENOTSUP, "layernorm: D must be 128*k, k in {1..12, 16}");
+  VP_HIP(e);
+  return VP_OK;
+}
+
+// Not in the public header: gather_frames (vp_kernels.h), the one launch vp_forward_temporal adds to vp_forward's, on
+// its own for kernel tests (tests/test_gpu_windows.py): x = states [F] of frame_bytes each, frame_idx device int32
+// [nslots] (clamped to [0, F - 1] by the kernel) -> out [nslots] frames.
+int vp_dev_gather_frames(const void* x, int64_t F, const int32_t* frame_idx, int64_t nslots, int64_t frame_bytes,
+                         void* out, void* stream) {
+  if (!x || !frame_idx || !out) return fail(VP_EINVAL, "null argument");
+  hipError_t e = vp::gather_frames(x, F, frame_idx, nslots, frame_bytes, out, static_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue)
+    return fail(VP_EINVAL, "gather_frames: 1 <= F, nslots < 2^31, frames of 16 k bytes (k <= 2^26), 16-byte aligned");
+  VP_HIP(e);
+  return VP_OK;
+}
+
+// Not in the public header: the two launches with which vp_forward_temporal enters the temporal half, gather_frames
+// into `scratch` ([rows][D] in x's dtype) and then layernorm on it, for kernel tests (tests/test_gpu_windows.py):
+// x = states [F][Nsp][D], frame_idx device int32 [rows / Nsp], rows = Wn*T*Nsp; perm 0 or 1; add (nullable) fp32
+// [T][D] by the output row's t; out_rs (nullable) [rows][2], (rstd, -mean*rstd) of each stored row by output row.
+int vp_dev_layernorm_gather(const void* x, int in_dtype, int64_t F, const int32_t* frame_idx, int64_t rows, int64_t D,
+                            const float* gamma, const float* beta, void* out, int out_dtype, int perm, int64_t T,
+                            int64_t Nsp, const float* add, float* out_rs, void* scratch, void* stream) {
+  using namespace vp;
+  if (!x || !frame_idx || !gamma || !beta || !out || !scratch) return fail(VP_EINVAL, "null argument");
+  if ((in_dtype != VP_F32 && in_dtype != VP_BF16) || (out_dtype != VP_F32 && out_dtype != VP_BF16))
+    return fail(VP_EINVAL, "bad dtype");
+  if (F < 1 || T < 1 || Nsp < 1 || rows < 1 || rows > 0x7fffffff || rows % Nsp ||
+      (perm != PERM_NONE && perm != PERM_BTN_TO_BNT) || (perm && rows % (T * Nsp)))
+    return fail(VP_EINVAL, "bad gather geometry");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = gather_frames(x, F, frame_idx, rows / Nsp, Nsp * D * (int64_t)dtype_bytes(in_dtype), scratch, s);
+  if (e == hipErrorInvalidValue) return fail(VP_EINVAL, "gather_frames: frames of 16 k bytes, 16-byte aligned");
+  VP_HIP(e);
+  e = layernorm(scratch, in_dtype == VP_BF16, (int)rows, (int)D, gamma, beta, out, out_dtype == VP_BF16, perm, (int)T,
+                (int)Nsp, add, s, out_rs);
   if (e == hipErrorInvalidValue) return fail(VP_ENOTSUP, "layernorm: D must be 128*k, k in {1..12, 16}");
   VP_HIP(e);
   return VP_OK;

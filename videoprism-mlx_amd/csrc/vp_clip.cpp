@@ -307,7 +307,25 @@ struct VisionFeat {
   PoolScratch sc;
 };
 
-int vision_features(WrapHandle* w, const void* video, int in_dtype, int64_t B, int64_t T, int64_t H, int64_t W,
+// Where vision_features takes its B clips from: frames [B, T, H, W, 3] (vp_forward), or, with states set, B windows
+// of T frames picked by frame_idx [B, T] out of the encoder's F frame states (vp_forward_temporal)
+struct VideoSrc {
+  const void* video = nullptr;
+  int in_dtype = VP_F32;
+  const void* states = nullptr;
+  int64_t F = 0;
+  const int32_t* frame_idx = nullptr;
+
+  // the source of the clips from b0 on
+  VideoSrc from(int64_t b0, int64_t T, size_t clip_bytes) const {
+    VideoSrc s = *this;
+    s.video = advance(video, b0 * clip_bytes);
+    s.frame_idx = frame_idx ? frame_idx + b0 * T : nullptr;
+    return s;
+  }
+};
+
+int vision_features(WrapHandle* w, const VideoSrc& src, int64_t B, int64_t T, int64_t H, int64_t W,
                     const float* frame_paddings, void* spatial_out, void* spatiotemporal_out, void* workspace,
                     void* stream, VisionFeat* vf) {
   ClipVideoWs& L = vf->L;
@@ -319,8 +337,10 @@ int vision_features(WrapHandle* w, const void* video, int in_dtype, int64_t B, i
   vf->M = (int)M64;
   char* ws = static_cast<char*>(workspace);
   vf->feat = ws + L.feat;
-  rc = vp_forward(w->video, video, in_dtype, B, T, H, W, frame_paddings, vf->feat, v.fprop_dtype, spatial_out,
-                  ws + L.inner, L.inner_bytes, stream);
+  rc = src.states ? vp_forward_temporal(w->video, src.states, src.F, src.frame_idx, B, T, H, W, frame_paddings, vf->feat,
+                                        v.fprop_dtype, spatial_out, ws + L.inner, L.inner_bytes, stream)
+                  : vp_forward(w->video, src.video, src.in_dtype, B, T, H, W, frame_paddings, vf->feat, v.fprop_dtype,
+                               spatial_out, ws + L.inner, L.inner_bytes, stream);
   if (rc) return rc;
   VP_HIP(hipSetDevice(w->device));
   if (spatiotemporal_out)
@@ -423,14 +443,13 @@ int vp_clip_video_workspace_bytes(const vp_clip* c, int64_t B, int64_t T, int64_
 namespace {
 
 // video side of FactorizedVideoCLIP over one chunk of B <= chunk_clips clips
-int clip_video_chunk(vp_clip* c, const void* video, int in_dtype, int64_t B, int64_t T, int64_t H, int64_t W,
+int clip_video_chunk(vp_clip* c, const VideoSrc& src, int64_t B, int64_t T, int64_t H, int64_t W,
                      const float* frame_paddings, int normalize, float* video_emb, float* frame_emb,
                      void* spatial_out, void* spatiotemporal_out, void* workspace, void* stream) {
   using namespace vp;
   // 1. vision encoder -> vision_features [B, T*N, D] (encoders.py:833-845)
   VisionFeat vf;
-  int rc = vision_features(c, video, in_dtype, B, T, H, W, frame_paddings, spatial_out, spatiotemporal_out, workspace,
-                           stream, &vf);
+  int rc = vision_features(c, src, B, T, H, W, frame_paddings, spatial_out, spatiotemporal_out, workspace, stream, &vf);
   if (rc) return rc;
   const bool bf = c->bf16();
   const vp_config& v = c->cfg.video;
@@ -471,6 +490,26 @@ int clip_video_chunk(vp_clip* c, const void* video, int in_dtype, int64_t B, int
   return VP_OK;
 }
 
+// vp_clip_encode_video / vp_clip_encode_video_windows over the B clips of `src`
+int clip_encode(vp_clip* c, const VideoSrc& src, int64_t B, int64_t T, int64_t H, int64_t W, const float* frame_paddings,
+                int normalize, float* video_emb, float* frame_emb, void* spatial_out, void* spatiotemporal_out,
+                int out_dtype, void* workspace, size_t ws_bytes, void* stream) {
+  if (!c->finalized) return fail(VP_ESTATE, "vp_clip_finalize has not been called");
+  size_t need = 0, st_clip = 0;
+  int rc = check_dtypes(src.in_dtype, out_dtype, spatiotemporal_out != nullptr, c->video->cfg.fprop_dtype);
+  if (rc || (rc = vp_clip_video_workspace_bytes(c, B, T, H, W, &need)) ||
+      (rc = check_workspace(c->video, T, H, W, ws_bytes, need, c->video->cfg.fprop_dtype, &st_clip)))
+    return rc;
+  const size_t in_clip = video_clip_bytes(T, H, W, src.in_dtype);
+  const int64_t D = c->cfg.video.model_dim;
+  return for_each_chunk(c->video, B, T, H, W, [&](int64_t b0, int64_t nb) {
+    return clip_video_chunk(c, src.from(b0, T, in_clip), nb, T, H, W, advance(frame_paddings, b0 * T * 4),
+                            normalize, video_emb + b0 * D, advance(frame_emb, b0 * T * D * 4),
+                            advance(spatial_out, b0 * st_clip), advance(spatiotemporal_out, b0 * st_clip), workspace,
+                            stream);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -480,20 +519,30 @@ int vp_clip_encode_video(vp_clip* c, const void* video, int in_dtype, int64_t B,
                          void* spatial_out, void* spatiotemporal_out, int out_dtype, void* workspace,
                          size_t ws_bytes, void* stream) {
   if (!c || !video || !video_emb || !workspace) return fail(VP_EINVAL, "null argument");
-  if (!c->finalized) return fail(VP_ESTATE, "vp_clip_finalize has not been called");
-  size_t need = 0, st_clip = 0;
-  int rc = check_dtypes(in_dtype, out_dtype, spatiotemporal_out != nullptr, c->video->cfg.fprop_dtype);
-  if (rc || (rc = vp_clip_video_workspace_bytes(c, B, T, H, W, &need)) ||
-      (rc = check_workspace(c->video, T, H, W, ws_bytes, need, c->video->cfg.fprop_dtype, &st_clip)))
-    return rc;
-  const size_t in_clip = video_clip_bytes(T, H, W, in_dtype);
-  const int64_t D = c->cfg.video.model_dim;
-  return for_each_chunk(c->video, B, T, H, W, [&](int64_t b0, int64_t nb) {
-    return clip_video_chunk(c, advance(video, b0 * in_clip), in_dtype, nb, T, H, W, advance(frame_paddings, b0 * T * 4),
-                            normalize, video_emb + b0 * D, advance(frame_emb, b0 * T * D * 4),
-                            advance(spatial_out, b0 * st_clip), advance(spatiotemporal_out, b0 * st_clip), workspace,
-                            stream);
-  });
+  VideoSrc src;
+  src.video = video;
+  src.in_dtype = in_dtype;
+  return clip_encode(c, src, B, T, H, W, frame_paddings, normalize, video_emb, frame_emb, spatial_out,
+                     spatiotemporal_out, out_dtype, workspace, ws_bytes, stream);
+}
+
+int vp_clip_video_windows_workspace_bytes(const vp_clip* c, int64_t Wn, int64_t T, int64_t H, int64_t W,
+                                          size_t* bytes) {
+  return vp_clip_video_workspace_bytes(c, Wn, T, H, W, bytes);
+}
+
+int vp_clip_encode_video_windows(vp_clip* c, const void* states, int64_t F, const int32_t* frame_idx, int64_t Wn,
+                                 int64_t T, int64_t H, int64_t W, const float* frame_paddings, int normalize,
+                                 float* video_emb, float* frame_emb, void* spatial_out, void* spatiotemporal_out,
+                                 int out_dtype, void* workspace, size_t ws_bytes, void* stream) {
+  if (!c || !states || !frame_idx || !video_emb || !workspace) return fail(VP_EINVAL, "null argument");
+  VideoSrc src;
+  src.in_dtype = c->video->cfg.fprop_dtype;
+  src.states = states;
+  src.F = F;
+  src.frame_idx = frame_idx;
+  return clip_encode(c, src, Wn, T, H, W, frame_paddings, normalize, video_emb, frame_emb, spatial_out,
+                     spatiotemporal_out, out_dtype, workspace, ws_bytes, stream);
 }
 
 int vp_clip_text_workspace_bytes(const vp_clip* c, int64_t Q, int64_t L, size_t* bytes) {
@@ -618,14 +667,13 @@ int vp_classifier_workspace_bytes(const vp_classifier* c, int64_t B, int64_t T, 
 namespace {
 
 // FactorizedVideoClassifier over one chunk of B <= chunk_clips clips
-int classifier_chunk(vp_classifier* c, const void* video, int in_dtype, int64_t B, int64_t T, int64_t H,
+int classifier_chunk(vp_classifier* c, const VideoSrc& src, int64_t B, int64_t T, int64_t H,
                      int64_t W, const float* frame_paddings, float* logits, float* embeddings,
                      void* spatial_out, void* spatiotemporal_out, void* workspace, void* stream) {
   using namespace vp;
   // 1. encoder -> features [B, T*N, D] (encoders.py:621-630)
   VisionFeat vf;
-  int rc = vision_features(c, video, in_dtype, B, T, H, W, frame_paddings, spatial_out, spatiotemporal_out, workspace,
-                           stream, &vf);
+  int rc = vision_features(c, src, B, T, H, W, frame_paddings, spatial_out, spatiotemporal_out, workspace, stream, &vf);
   if (rc) return rc;
   const vp_config& v = c->cfg;
   const int D = v.model_dim, NH = v.num_heads, M = vf.M;
@@ -640,6 +688,26 @@ int classifier_chunk(vp_classifier* c, const void* video, int in_dtype, int64_t 
   return VP_OK;
 }
 
+// vp_classifier_forward / vp_classifier_forward_windows over the B clips of `src`
+int classifier_run(vp_classifier* c, const VideoSrc& src, int64_t B, int64_t T, int64_t H, int64_t W,
+                   const float* frame_paddings, float* logits, float* embeddings, void* spatial_out,
+                   void* spatiotemporal_out, int out_dtype, void* workspace, size_t ws_bytes, void* stream) {
+  if (!c->finalized) return fail(VP_ESTATE, "vp_classifier_finalize has not been called");
+  size_t need = 0, st_clip = 0;
+  int rc = check_dtypes(src.in_dtype, out_dtype, spatiotemporal_out != nullptr, c->cfg.fprop_dtype);
+  if (rc || (rc = vp_classifier_workspace_bytes(c, B, T, H, W, &need)) ||
+      (rc = check_workspace(c->video, T, H, W, ws_bytes, need, c->video->cfg.fprop_dtype, &st_clip)))
+    return rc;
+  const size_t in_clip = video_clip_bytes(T, H, W, src.in_dtype);
+  const int64_t D = c->cfg.model_dim;
+  return for_each_chunk(c->video, B, T, H, W, [&](int64_t b0, int64_t nb) {
+    return classifier_chunk(c, src.from(b0, T, in_clip), nb, T, H, W, advance(frame_paddings, b0 * T * 4),
+                            logits + b0 * c->num_classes, advance(embeddings, b0 * D * 4),
+                            advance(spatial_out, b0 * st_clip), advance(spatiotemporal_out, b0 * st_clip), workspace,
+                            stream);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -649,20 +717,30 @@ int vp_classifier_forward(vp_classifier* c, const void* video, int in_dtype, int
                           void* spatial_out, void* spatiotemporal_out, int out_dtype, void* workspace,
                           size_t ws_bytes, void* stream) {
   if (!c || !video || !logits || !workspace) return fail(VP_EINVAL, "null argument");
-  if (!c->finalized) return fail(VP_ESTATE, "vp_classifier_finalize has not been called");
-  size_t need = 0, st_clip = 0;
-  int rc = check_dtypes(in_dtype, out_dtype, spatiotemporal_out != nullptr, c->cfg.fprop_dtype);
-  if (rc || (rc = vp_classifier_workspace_bytes(c, B, T, H, W, &need)) ||
-      (rc = check_workspace(c->video, T, H, W, ws_bytes, need, c->video->cfg.fprop_dtype, &st_clip)))
-    return rc;
-  const size_t in_clip = video_clip_bytes(T, H, W, in_dtype);
-  const int64_t D = c->cfg.model_dim;
-  return for_each_chunk(c->video, B, T, H, W, [&](int64_t b0, int64_t nb) {
-    return classifier_chunk(c, advance(video, b0 * in_clip), in_dtype, nb, T, H, W, advance(frame_paddings, b0 * T * 4),
-                            logits + b0 * c->num_classes, advance(embeddings, b0 * D * 4),
-                            advance(spatial_out, b0 * st_clip), advance(spatiotemporal_out, b0 * st_clip), workspace,
-                            stream);
-  });
+  VideoSrc src;
+  src.video = video;
+  src.in_dtype = in_dtype;
+  return classifier_run(c, src, B, T, H, W, frame_paddings, logits, embeddings, spatial_out, spatiotemporal_out,
+                        out_dtype, workspace, ws_bytes, stream);
+}
+
+int vp_classifier_windows_workspace_bytes(const vp_classifier* c, int64_t Wn, int64_t T, int64_t H, int64_t W,
+                                          size_t* bytes) {
+  return vp_classifier_workspace_bytes(c, Wn, T, H, W, bytes);
+}
+
+int vp_classifier_forward_windows(vp_classifier* c, const void* states, int64_t F, const int32_t* frame_idx,
+                                  int64_t Wn, int64_t T, int64_t H, int64_t W, const float* frame_paddings,
+                                  float* logits, float* embeddings, void* spatial_out, void* spatiotemporal_out,
+                                  int out_dtype, void* workspace, size_t ws_bytes, void* stream) {
+  if (!c || !states || !frame_idx || !logits || !workspace) return fail(VP_EINVAL, "null argument");
+  VideoSrc src;
+  src.in_dtype = c->video->cfg.fprop_dtype;
+  src.states = states;
+  src.F = F;
+  src.frame_idx = frame_idx;
+  return classifier_run(c, src, Wn, T, H, W, frame_paddings, logits, embeddings, spatial_out, spatiotemporal_out,
+                        out_dtype, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

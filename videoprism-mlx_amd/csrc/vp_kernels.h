@@ -168,6 +168,12 @@ hipError_t patchify(const void* video, int in_dtype, void* patches, int out_is_b
 hipError_t layernorm(const void* x, int in_is_bf16, int rows, int D, const float* gamma,
                      const float* beta, void* out, int out_is_bf16, int perm, int T, int Nsp,
                      const float* add, hipStream_t s, float* out_rs = nullptr);
+// The frames of a batch of windows picked out of per-frame states x [nframes] of frame_bytes each (a multiple of 16,
+// x and out 16-byte aligned): out frame s = x frame clamp(frame_idx[s], 0, nframes - 1), s < nslots (frame_idx: int32
+// [nslots] in device memory).  The clamp is part of the contract: an index out of range is the caller's error, but no
+// read leaves x.  A copy, so whatever runs on `out` gives bitwise what it gives on the gathered frames themselves.
+hipError_t gather_frames(const void* x, int64_t nframes, const int32_t* frame_idx, int64_t nslots, int64_t frame_bytes,
+                         void* out, hipStream_t s);
 // norm_policy 'primer_hybrid' (layers.py:409-425, :846-855): xs[r] += LayerNorm(y[r] * (1 - pad[r])) in place on the
 // fp32 residual stream; y fp32 or bf16 rows of D = 128 k (layernorm's widths), gamma = 1 + scale, pad optional
 // [rows] (1 = padded token: the row gets xs + beta)

@@ -82,6 +82,29 @@ _SIGNATURES = {
     "vp_workspace_bytes": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
     "vp_forward": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_void_p,
                            c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # sliding windows: per-frame spatial states once, then the temporal half over windows of them
+    "vp_spatial_workspace_bytes": (c_int, [c_void_p, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "vp_forward_spatial": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                   c_void_p, c_size_t, c_void_p]),
+    "vp_temporal_workspace_bytes": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, POINTER(c_size_t)]),
+    "vp_forward_temporal": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                    c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_clip_video_windows_workspace_bytes": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                                      POINTER(c_size_t)]),
+    "vp_clip_encode_video_windows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                             c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_int, c_void_p, c_size_t, c_void_p]),
+    "vp_classifier_windows_workspace_bytes": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                                      POINTER(c_size_t)]),
+    "vp_classifier_forward_windows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                                              c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                              c_void_p, c_size_t, c_void_p]),
+    # not in the public header: the frame gather of vp_forward_temporal on its own
+    "vp_dev_gather_frames": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    # ... followed by the LayerNorm, as vp_forward_temporal launches the two
+    "vp_dev_layernorm_gather": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
+                                        c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
     "vp_profile_enable": (c_int, [c_void_p, c_int]),
     "vp_profile_read": (c_int, [c_void_p, c_int, POINTER(ctypes.c_double), POINTER(ctypes.c_double),
                                 POINTER(ctypes.c_double), POINTER(c_int64)]),
@@ -543,6 +566,30 @@ def op_layernorm(x, gamma1p, beta, out_dtype=None, perm=PERM_NONE, T=1, Nsp=1, a
     call("vp_op_layernorm", _ptr(x), _prec(x), rows, D, _ptr(gamma1p), _ptr(beta), _ptr(out),
          VP_BF16 if out_dtype == torch.bfloat16 else VP_F32, perm, T, Nsp, _ptr(add),
          _stream(stream))
+    return out
+
+
+def dev_gather_frames(states, frame_idx, out, stream=None):
+    """out[s] = states[clamp(frame_idx[s], 0, F - 1)]: states [F, ...] contiguous, frame_idx int32 [nslots] on the
+    device, out [nslots, ...] of the same dtype (written in place: the caller prefills it)."""
+    F = states.shape[0]
+    frame_bytes = states[0].numel() * states.element_size()
+    call("vp_dev_gather_frames", _ptr(states), F, _ptr(frame_idx), frame_idx.numel(), frame_bytes, _ptr(out),
+         _stream(stream))
+    return out
+
+
+def dev_layernorm_gather(states, frame_idx, T, gamma1p, beta, out, perm=PERM_NONE, add=None, out_rs=None,
+                         stream=None):
+    """gather_frames, then LayerNorm, as vp_forward_temporal launches them: states [F, Nsp, D], frame_idx int32
+    [Wn*T] on the device (clamped to [0, F - 1] by the kernel), out [Wn*T*Nsp, D] bf16 / fp32 and out_rs (optional)
+    fp32 [Wn*T*Nsp, 2] by output row, both written in place (the caller prefills them)."""
+    import torch
+    F, Nsp, D = states.shape
+    rows = frame_idx.numel() * Nsp
+    scratch = torch.empty((rows, D), dtype=states.dtype, device=states.device)
+    call("vp_dev_layernorm_gather", _ptr(states), _prec(states), F, _ptr(frame_idx), rows, D, _ptr(gamma1p),
+         _ptr(beta), _ptr(out), _prec(out), perm, T, Nsp, _ptr(add), _ptr(out_rs), _ptr(scratch), _stream(stream))
     return out
 
 

@@ -68,6 +68,130 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+class FrameStates:
+    """Per-frame spatial states of one frame size: what `encode_frames` computes once per frame and
+    `apply_windows` reads any number of windows from.
+
+      states      CUDA tensor [F, N, D] in the model's fprop dtype: the spatial residual stream after the last
+                  spatial layer, before spatial_ln (not the reference's post-LN 'spatial_features')
+      paddings    CUDA fp32 tensor [F] (1 = padded frame) or None
+      frame_size  (H, W) of the frames
+
+    A state depends on its frame's pixels and padding only, so states may be sliced (`fs[a:b]`) and concatenated
+    (`FrameStates.cat([...])`) freely: a stream appends the new frames' states and drops the old ones."""
+
+    def __init__(self, states, paddings, frame_size):
+        if states.dim() != 3:
+            raise ValueError(f"states must be [F, N, D], got {tuple(states.shape)}")
+        if paddings is not None and tuple(paddings.shape) != (states.shape[0],):
+            raise ValueError(f"paddings must be [{states.shape[0]}], got {tuple(paddings.shape)}")
+        self.states = states
+        self.paddings = paddings
+        self.frame_size = (int(frame_size[0]), int(frame_size[1]))
+
+    def __len__(self) -> int:
+        return self.states.shape[0]
+
+    def __getitem__(self, key) -> "FrameStates":
+        if not isinstance(key, slice):
+            raise TypeError("FrameStates takes slices only (fs[a:b]); windows pick single frames by frame_index")
+        return FrameStates(self.states[key], None if self.paddings is None else self.paddings[key], self.frame_size)
+
+    @staticmethod
+    def cat(parts) -> "FrameStates":
+        """The states of `parts` (FrameStates of one model and frame size) one after the other; frames of a part
+        without paddings count as unpadded when another part has them."""
+        parts = list(parts)
+        if not parts:
+            raise ValueError("FrameStates.cat needs at least one part")
+        torch = _torch()
+        first = parts[0]
+        for q in parts[1:]:
+            if q.frame_size != first.frame_size or q.states.shape[1:] != first.states.shape[1:] or \
+                    q.states.dtype != first.states.dtype or q.states.device != first.states.device:
+                raise ValueError("FrameStates.cat: parts differ in frame size, widths, dtype or device")
+        full = [q for q in parts if len(q)]
+        if len(full) == 1:  # nothing to join: no copy
+            return full[0]
+        pads = None
+        if any(q.paddings is not None for q in parts):
+            pads = torch.cat([q.paddings if q.paddings is not None else
+                              torch.zeros(len(q), dtype=torch.float32, device=q.states.device) for q in parts])
+        return FrameStates(torch.cat([q.states for q in parts]), pads, first.frame_size)
+
+
+def _frames_on_device(frames, bf16: bool):
+    """[F, H, W, 3] frames as `apply` moves clips: numpy -> the current device (uint8 as bytes, anything else as
+    fp32), host tensors -> the current device, fp32 -> bf16 for a bf16 model.  -> (CUDA tensor, device index)."""
+    torch = _torch()
+    if isinstance(frames, torch.Tensor):
+        x = frames
+        if not x.is_cuda:
+            x = x.to(f"cuda:{torch.cuda.current_device()}")
+    else:
+        arr = np.asarray(frames)
+        x = torch.from_numpy(np.ascontiguousarray(arr if arr.dtype == np.uint8 else
+                                                  arr.astype(np.float32, copy=False)))
+        x = x.to(f"cuda:{torch.cuda.current_device()}")
+    if x.dim() != 4:
+        raise ValueError(f"frames must be [F, H, W, 3], got {tuple(x.shape)}")
+    assert x.shape[1] == x.shape[2]  # encoders.py:435
+    if bf16 and x.dtype == torch.float32:
+        x = x.to(torch.bfloat16)
+    return x, x.device.index
+
+
+class _CheckedIndex:
+    """A frame_index [Wn, T] that `_frame_index` has already validated against `num_frames` states."""
+
+    def __init__(self, tensor, num_frames: int):
+        self.tensor = tensor
+        self.num_frames = num_frames
+
+
+def _frame_index(frame_index, num_frames: int):
+    """frame_index [Wn, T] as a torch integer tensor.  A host index (numpy, list, CPU tensor) is range-checked
+    against the `num_frames` states (IndexError) and comes back as a CPU int32 tensor; a CUDA tensor comes back as it
+    is, unchecked, since reading it would synchronise: the kernel clamps it to the states.  A _CheckedIndex for the
+    same number of states is not checked again."""
+    torch = _torch()
+    if isinstance(frame_index, _CheckedIndex) and frame_index.num_frames == num_frames:
+        return frame_index.tensor
+    if isinstance(frame_index, torch.Tensor) and frame_index.is_cuda:
+        if frame_index.dtype.is_floating_point or frame_index.dtype == torch.bool:
+            raise TypeError("frame_index must be an integer tensor")
+        idx = frame_index
+    else:
+        host = frame_index.numpy() if isinstance(frame_index, torch.Tensor) else np.asarray(frame_index)
+        if host.dtype.kind not in "iu":
+            raise TypeError("frame_index must hold integers")
+        if host.size and (int(host.min()) < 0 or int(host.max()) >= num_frames):
+            raise IndexError(f"frame_index out of range for {num_frames} frames: "
+                             f"[{int(host.min())}, {int(host.max())}]")
+        idx = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32)))
+    if idx.dim() != 2 or idx.shape[1] < 1:
+        raise ValueError(f"frame_index must be [Wn, T] with T >= 1, got {tuple(idx.shape)}")
+    if idx.shape[0] > 0 and num_frames == 0:
+        raise IndexError("frame_index points into states that hold no frames")
+    return idx
+
+
+def _states_device(states) -> int:
+    """The device index of the FrameStates handed to apply_windows."""
+    if not isinstance(states, FrameStates):
+        raise TypeError("states must be the FrameStates that encode_frames returns")
+    if not states.states.is_cuda:
+        raise ValueError(f"states must be on a cuda device, got {states.states.device}")
+    return states.states.device.index
+
+
+def _as_paddings(p):
+    torch = _torch()
+    if p is None or isinstance(p, torch.Tensor):
+        return p
+    return torch.from_numpy(np.asarray(p, dtype=np.float32))
+
+
 class _EngineBase:
     """One native handle (packed weights on one device) plus its grow-only workspaces.  A subclass
     names its C entry points (`_PREFIX`_create / _set_param / _finalize / _destroy) and gives the
@@ -141,10 +265,10 @@ class _EngineBase:
         """Short symbol of the kernel behind profiler class `cls_name` (last launch)."""
         return _native.profile_kernel_name(self.video_handle(), cls_name)
 
-    def _workspace(self, key: str, query: str, *dims):
+    def _workspace(self, key: str, query: str, *dims, handle=None):
         """The cached workspace `key`, regrown if `query`(handle, *dims, &bytes) asks for more."""
         n = ctypes.c_size_t()
-        _native.call(query, self._h, *dims, ctypes.byref(n))
+        _native.call(query, self._h if handle is None else handle, *dims, ctypes.byref(n))
         ws = self._ws.get(key)
         if ws is None or ws.numel() < n.value:
             ws = self._ws[key] = None  # the old one is freed before the new one is allocated
@@ -190,6 +314,62 @@ class _EngineBase:
         # uint8 frames are normalised /255 on device
         return video, _native._prec(video), fp, B, T, H, W, (H // P) * (W // P)
 
+    # -- sliding windows: per-frame states once, then windows of them -------------------
+    def encode_frames(self, frames, frame_paddings=None, stream=None) -> FrameStates:
+        """frames: CUDA tensor [F, H, W, 3] (fp32, bf16 or uint8) on this engine's device; frame_paddings [F] or
+        None.  The spatial half of the encoder, once per frame (vp_forward_spatial)."""
+        torch = _torch()
+        if frames.dim() != 4:
+            raise ValueError(f"frames must be [F, H, W, 3], got {tuple(frames.shape)}")
+        fp = None if frame_paddings is None else frame_paddings.reshape(-1, 1)
+        video, in_dt, fp, F, _, H, W, N = self._check_video(frames.unsqueeze(1), fp)
+        states = torch.empty((F, N, self.cfg["model_dim"]), dtype=torch.bfloat16 if self.bf16 else torch.float32,
+                             device=video.device)
+        fp = None if fp is None else fp.reshape(F)
+        if F > 0:
+            vh = self.video_handle()
+            ws = self._workspace("spatial", "vp_spatial_workspace_bytes", F, H, W, handle=vh)
+            _native.call("vp_forward_spatial", vh, _ptr(video), in_dt, F, H, W, _ptr(fp), _ptr(states), _ptr(ws),
+                         ws.numel(), self._stream(stream))
+        return FrameStates(states, fp, (H, W))
+
+    def _check_windows(self, fs: FrameStates, frame_index):
+        """-> (states [F, N, D] contiguous, frame_index as device int32 [Wn, T], the windows' frame paddings [Wn, T]
+        fp32 or None, F, Wn, T, H, W, N), with the temporal table for T prepared.  A host frame_index is
+        range-checked (IndexError); a CUDA tensor is not, since that would synchronise: the kernel clamps it."""
+        torch = _torch()
+        if not isinstance(fs, FrameStates):
+            raise TypeError("states must be the FrameStates that encode_frames returns")
+        st = fs.states
+        _check_device(st, self.device, "states")
+        H, W = fs.frame_size
+        P, D = self.cfg["patch_size"], self.cfg["model_dim"]
+        if H % P or W % P:
+            raise ValueError(f"Image height ({H}) and width ({W}) should be multiples of patch_size ({P}).")
+        N = (H // P) * (W // P)
+        want = torch.bfloat16 if self.bf16 else torch.float32
+        if st.dim() != 3 or tuple(st.shape[1:]) != (N, D):
+            raise ValueError(f"states must be [F, {N}, {D}] for this model and frame size, got {tuple(st.shape)}")
+        if st.dtype != want:
+            raise ValueError(f"states must be {want} (this model's fprop dtype), got {st.dtype}")
+        F = st.shape[0]
+        idx = _frame_index(frame_index, F)
+        if idx.is_cuda:
+            _check_device(idx, self.device, "frame_index")
+        Wn, T = idx.shape
+        idx = idx.to(device=st.device, dtype=torch.int32).contiguous()
+        fp = None
+        if fs.paddings is not None and Wn > 0:
+            _check_device(fs.paddings, self.device, "states.paddings")
+            fp = fs.paddings.to(torch.float32)[idx.clamp(0, F - 1).long()].contiguous()
+        if T not in self._grids:
+            _native.call("vp_prepare_frames", self.video_handle(), T)
+            self._grids.add(T)
+        if (H, W) not in self._grids:  # states carried over from another engine of the same model
+            _native.call("vp_prepare_geometry", self.video_handle(), H, W)
+            self._grids.add((H, W))
+        return st.contiguous(), idx, fp, F, Wn, T, H, W, N
+
     def _features(self, want: bool, B: int, L: int, device):
         """A [B, L, D] buffer in the fprop dtype for spatial / spatio-temporal features, if wanted."""
         torch = _torch()
@@ -231,6 +411,21 @@ class Engine(_EngineBase):
             return out, sp
         ws = self.workspace(B, T, H, W)
         _native.call("vp_forward", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp), _ptr(out),
+                     _native._prec(out), _ptr(sp), _ptr(ws), ws.numel(), self._stream(stream))
+        return out, sp
+
+    def forward_windows(self, fs: FrameStates, frame_index, out_dtype=None, want_spatial=False, stream=None):
+        """The temporal half over windows of frame states (vp_forward_temporal): frame_index int [Wn, T] ->
+        embeddings [Wn, T*N, D], bitwise `forward` on the gathered clips."""
+        torch = _torch()
+        st, idx, fp, F, Wn, T, H, W, N = self._check_windows(fs, frame_index)
+        out_dtype = out_dtype or (torch.bfloat16 if self.bf16 else torch.float32)
+        out = torch.empty((Wn, T * N, self.cfg["model_dim"]), dtype=out_dtype, device=st.device)
+        sp = torch.empty_like(out) if want_spatial else None
+        if Wn == 0:  # no windows: a zero-size result, nothing to launch
+            return out, sp
+        ws = self._workspace("video", "vp_temporal_workspace_bytes", Wn, T, H, W)
+        _native.call("vp_forward_temporal", self._h, _ptr(st), F, _ptr(idx), Wn, T, H, W, _ptr(fp), _ptr(out),
                      _native._prec(out), _ptr(sp), _ptr(ws), ws.numel(), self._stream(stream))
         return out, sp
 
@@ -344,6 +539,35 @@ class FactorizedEncoder:
 
     __call__ = apply
 
+    def encode_frames(self, variables, frames, frame_paddings=None) -> FrameStates:
+        """The spatial half (encoders.py:459-478 and what feeds it) of `frames` [F, H, W, 3] (numpy or CUDA
+        tensor; fp32, bf16 or uint8), frame_paddings [F] or None, once per frame -> FrameStates for
+        `apply_windows`.  Overlapping windows of one long video share these states."""
+        x, device = _frames_on_device(frames, self.is_bf16)
+        return self.engine(variables, device).encode_frames(x, _as_paddings(frame_paddings))
+
+    def apply_windows(self, variables, states: FrameStates, frame_index, train: bool = False,
+                      return_intermediate: bool | Collection[str] = False):
+        """`apply` over windows of frame states -> (embeddings [Wn, T*N, D], outputs): window w is the frames
+        states[frame_index[w, t]], t = 0..T-1 (video_utils.sliding_windows builds the usual index), with the
+        frames' paddings.  Bit for bit `apply(frames[frame_index], frame_paddings=paddings[frame_index])`.
+        A host frame_index (numpy, list, CPU tensor) is range-checked (IndexError); a CUDA tensor is not (that
+        would synchronise) and is clamped to the states by the kernel.  Results are numpy arrays unless
+        frame_index is a torch tensor.  For a short last window, keep one padded frame among the states and
+        point the missing slots at it."""
+        del train
+        torch = _torch()
+        as_numpy = not isinstance(frame_index, torch.Tensor)
+        frame_index = _CheckedIndex(_frame_index(frame_index, len(states)), len(states))
+        eng = self.engine(variables, _states_device(states))
+        want_sp = _contains(return_intermediate, "spatial_features")
+        emb, sp = eng.forward_windows(states, frame_index, want_spatial=want_sp)
+        outputs = {"spatial_features": sp} if want_sp else {}
+        if as_numpy:
+            emb = emb.float().cpu().numpy()
+            outputs = {k: v.float().cpu().numpy() for k, v in outputs.items()}
+        return emb, outputs
+
 
 class ClipEngine(_EngineBase):
     """One vp_clip handle (packed LvT weights on one device) plus reusable workspaces."""
@@ -374,6 +598,26 @@ class ClipEngine(_EngineBase):
             return vemb, femb, sp, st
         ws = self._workspace("video", "vp_clip_video_workspace_bytes", B, T, H, W)
         _native.call("vp_clip_encode_video", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp),
+                     1 if normalize else 0, _ptr(vemb), _ptr(femb), _ptr(sp), _ptr(st),
+                     _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
+                     self._stream(stream))
+        return vemb, femb, sp, st
+
+    def encode_video_windows(self, fs: FrameStates, frame_index, normalize=True, want_frames=False,
+                             want_spatial=False, want_spatiotemporal=False, stream=None):
+        """encode_video over windows of the vision tower's frame states (vp_clip_encode_video_windows)."""
+        torch = _torch()
+        st_, idx, fp, F, Wn, T, H, W, N = self._check_windows(fs, frame_index)
+        D = self.cfg["model_dim"]
+        dev = st_.device
+        vemb = torch.empty((Wn, D), dtype=torch.float32, device=dev)
+        femb = torch.empty((Wn, T, D), dtype=torch.float32, device=dev) if want_frames else None
+        sp = self._features(want_spatial, Wn, T * N, dev)
+        st = self._features(want_spatiotemporal, Wn, T * N, dev)
+        if Wn == 0:
+            return vemb, femb, sp, st
+        ws = self._workspace("video", "vp_clip_video_windows_workspace_bytes", Wn, T, H, W)
+        _native.call("vp_clip_encode_video_windows", self._h, _ptr(st_), F, _ptr(idx), Wn, T, H, W, _ptr(fp),
                      1 if normalize else 0, _ptr(vemb), _ptr(femb), _ptr(sp), _ptr(st),
                      _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
                      self._stream(stream))
@@ -511,6 +755,59 @@ class FactorizedVideoCLIP:
 
     __call__ = apply
 
+    def encode_frames(self, variables, frames, frame_paddings=None) -> FrameStates:
+        """FactorizedEncoder.encode_frames on the vision tower."""
+        x, device = _frames_on_device(frames, self.is_bf16)
+        return self.engine(variables, device).encode_frames(x, _as_paddings(frame_paddings))
+
+    def apply_windows(self, variables, states: FrameStates = None, frame_index=None, text_token_ids=None,
+                      text_paddings=None, train: bool = False, normalize: bool = True,
+                      return_intermediate: bool | Collection[str] = False, **kwargs):
+        """`apply` with the video side over windows of frame states (FactorizedEncoder.apply_windows) ->
+        (video_embeddings [Wn, D] | None, text_embeddings | None, outputs); `states` (with frame_index) or the
+        text inputs may be None as in `apply`.  Results are numpy arrays unless frame_index or text_token_ids is a
+        torch tensor."""
+        del train
+        if kwargs.get("method") not in (None,):
+            raise NotImplementedError("apply_windows(method=...) is not supported")
+        torch = _torch()
+        as_numpy = not any(isinstance(t, torch.Tensor) for t in (frame_index, text_token_ids) if t is not None)
+        if states is not None:
+            assert frame_index is not None, "frame_index is required with states."
+            frame_index = _CheckedIndex(_frame_index(frame_index, len(states)), len(states))
+            device = _states_device(states)
+        elif isinstance(text_token_ids, torch.Tensor) and text_token_ids.is_cuda:
+            device = text_token_ids.device.index
+        else:
+            device = torch.cuda.current_device()
+        eng = self.engine(variables, device)
+        dev = f"cuda:{device}"
+        fdt = torch.bfloat16 if self.is_bf16 else torch.float32
+        video_emb = text_emb = None
+        outputs = {}
+        if states is not None:
+            vemb, femb, sp, st = eng.encode_video_windows(
+                states, frame_index, normalize, want_frames=_contains(return_intermediate, "frame_embeddings"),
+                want_spatial=_contains(return_intermediate, "spatial_features"),
+                want_spatiotemporal=_contains(return_intermediate, "spatiotemporal_features"))
+            video_emb = vemb.to(fdt)
+            for k, v in (("spatial_features", sp), ("spatiotemporal_features", st),
+                         ("frame_embeddings", femb)):
+                if v is not None:
+                    outputs[k] = v.to(fdt)
+        if text_token_ids is not None:
+            assert text_paddings is not None, "Text paddings are required."
+            ids = text_token_ids if isinstance(text_token_ids, torch.Tensor) else \
+                torch.from_numpy(np.asarray(text_token_ids, dtype=np.int32))
+            pads = text_paddings if isinstance(text_paddings, torch.Tensor) else \
+                torch.from_numpy(np.asarray(text_paddings, dtype=np.float32))
+            text_emb = eng.encode_text(ids.to(dev), pads.to(dev), normalize).to(fdt)
+        if as_numpy:
+            cvt = lambda t: None if t is None else t.float().cpu().numpy()  # noqa: E731
+            video_emb, text_emb = cvt(video_emb), cvt(text_emb)
+            outputs = {k: cvt(v) for k, v in outputs.items()}
+        return video_emb, text_emb, outputs
+
 
 class ClassifierEngine(_EngineBase):
     """One vp_classifier handle (FactorizedVideoClassifier weights on one device)."""
@@ -538,6 +835,26 @@ class ClassifierEngine(_EngineBase):
             return logits, emb, sp, st
         ws = self._workspace("video", "vp_classifier_workspace_bytes", B, T, H, W)
         _native.call("vp_classifier_forward", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp),
+                     _ptr(logits), _ptr(emb), _ptr(sp), _ptr(st),
+                     _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
+                     self._stream(stream))
+        return logits, emb, sp, st
+
+    def forward_windows(self, fs: FrameStates, frame_index, want_embeddings=False, want_spatial=False,
+                        want_spatiotemporal=False, stream=None):
+        """forward over windows of the encoder's frame states (vp_classifier_forward_windows)."""
+        torch = _torch()
+        st_, idx, fp, F, Wn, T, H, W, N = self._check_windows(fs, frame_index)
+        D = self.cfg["model_dim"]
+        dev = st_.device
+        logits = torch.empty((Wn, self.num_classes), dtype=torch.float32, device=dev)
+        emb = torch.empty((Wn, D), dtype=torch.float32, device=dev) if want_embeddings else None
+        sp = self._features(want_spatial, Wn, T * N, dev)
+        st = self._features(want_spatiotemporal, Wn, T * N, dev)
+        if Wn == 0:
+            return logits, emb, sp, st
+        ws = self._workspace("video", "vp_classifier_windows_workspace_bytes", Wn, T, H, W)
+        _native.call("vp_classifier_forward_windows", self._h, _ptr(st_), F, _ptr(idx), Wn, T, H, W, _ptr(fp),
                      _ptr(logits), _ptr(emb), _ptr(sp), _ptr(st),
                      _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
                      self._stream(stream))
@@ -622,3 +939,33 @@ class FactorizedVideoClassifier:
         return logits, outputs
 
     __call__ = apply
+
+    def encode_frames(self, variables, frames, frame_paddings=None) -> FrameStates:
+        """FactorizedEncoder.encode_frames on the classifier's encoder."""
+        x, device = _frames_on_device(frames, self.is_bf16)
+        return self.engine(variables, device).encode_frames(x, _as_paddings(frame_paddings))
+
+    def apply_windows(self, variables, states: FrameStates, frame_index, train: bool = False,
+                      return_intermediate: bool | Collection[str] = False):
+        """`apply` over windows of frame states (FactorizedEncoder.apply_windows) -> (logits [Wn, num_classes],
+        outputs)."""
+        del train
+        torch = _torch()
+        as_numpy = not isinstance(frame_index, torch.Tensor)
+        frame_index = _CheckedIndex(_frame_index(frame_index, len(states)), len(states))
+        eng = self.engine(variables, _states_device(states))
+        logits, emb, sp, st = eng.forward_windows(
+            states, frame_index, want_embeddings=_contains(return_intermediate, "global_embeddings"),
+            want_spatial=_contains(return_intermediate, "spatial_features"),
+            want_spatiotemporal=_contains(return_intermediate, "spatiotemporal_features"))
+        fdt = torch.bfloat16 if self.is_bf16 else torch.float32
+        logits = logits.to(fdt)
+        outputs = {}
+        for k, v in (("spatial_features", sp), ("spatiotemporal_features", st),
+                     ("global_embeddings", emb)):
+            if v is not None:
+                outputs[k] = v.to(fdt)
+        if as_numpy:
+            logits = logits.float().cpu().numpy()
+            outputs = {k: v.float().cpu().numpy() for k, v in outputs.items()}
+        return logits, outputs

@@ -88,6 +88,15 @@ class VideoEncoder:
                                   return_intermediate=return_intermediate,
                                   frame_paddings=frame_paddings)
 
+    def encode_frames(self, frames, frame_paddings=None):
+        """Per-frame spatial states of frames [F, H, W, 3], computed once (FactorizedEncoder.encode_frames)."""
+        return self.encoder.encode_frames(self.variables, frames, frame_paddings=frame_paddings)
+
+    def apply_windows(self, states, frame_index, return_intermediate=False):
+        """The model over windows of those states (FactorizedEncoder.apply_windows)."""
+        return self.encoder.apply_windows(self.variables, states, frame_index, train=False,
+                                          return_intermediate=return_intermediate)
+
 
 def load_video_encoder(model_name: str, weights_path: str = None, fprop_dtype=None) -> VideoEncoder:
     """models_mlx.py:146-210."""
@@ -121,6 +130,16 @@ class VideoCLIP:
                                 train=False, normalize=normalize,
                                 return_intermediate=return_intermediate,
                                 frame_paddings=frame_paddings)
+
+    def encode_frames(self, frames, frame_paddings=None):
+        """Per-frame spatial states of the vision tower (FactorizedVideoCLIP.encode_frames)."""
+        return self.model.encode_frames(self.variables, frames, frame_paddings=frame_paddings)
+
+    def apply_windows(self, states=None, frame_index=None, text_token_ids=None, text_paddings=None, normalize=True,
+                      return_intermediate=False):
+        """The model with its video side over windows of those states (FactorizedVideoCLIP.apply_windows)."""
+        return self.model.apply_windows(self.variables, states, frame_index, text_token_ids, text_paddings,
+                                        train=False, normalize=normalize, return_intermediate=return_intermediate)
 
 
 def load_model(model_name: str, weights_path: str = None, fprop_dtype=None) -> VideoCLIP:

@@ -31,6 +31,18 @@ def center_crop_geometry(h: int, w: int, target_size: int):
     return new_h, new_w, (new_h - target_size) // 2, (new_w - target_size) // 2
 
 
+def sliding_windows(num_frames_total: int, num_frames: int = 16, stride: int = 1, dilation: int = 1) -> np.ndarray:
+    """Frame indices of every full window over a video of `num_frames_total` frames, int32 [Wn, num_frames]:
+    window w holds frames w*stride + t*dilation, t = 0..num_frames-1 (`dilation` is the frame step inside a
+    window).  A video too short for one window gives [0, num_frames].  The `frame_index` of `apply_windows`."""
+    if num_frames_total < 0 or num_frames < 1 or stride < 1 or dilation < 1:
+        raise ValueError("sliding_windows needs num_frames_total >= 0 and num_frames, stride, dilation >= 1")
+    span = (num_frames - 1) * dilation + 1  # frames a window reaches over
+    count = (num_frames_total - span) // stride + 1 if num_frames_total >= span else 0
+    starts = np.arange(count, dtype=np.int64) * stride
+    return (starts[:, None] + np.arange(num_frames, dtype=np.int64)[None, :] * dilation).astype(np.int32)
+
+
 def _mode(resize_mode):
     if resize_mode not in _MODES:
         raise ValueError(f"Unknown resize_mode: {resize_mode}")
