@@ -31,13 +31,17 @@ rounding emulation), the Flax reference at /root/reference/videoprism:
   * encoders.py:656-759     TextEncoder (causal, ReLU, CLS token, unimodal_ln)
   * encoders.py:762-910     FactorizedVideoCLIP.__call__ (auxiliary encoder, pooler, L2)
 
-PARITY UNPINNED: the reference's own tests pin only shapes and parameter-leaf
-counts (encoders_test.py:170, models_test.py:52); JAX/Flax are not installed in
-this container (ModuleNotFoundError, not a permission denial), no checkpoint is
-available offline, and the reference ships no golden vectors for this path.  The
-restatement is therefore pinned only by those structural facts, by a second
-independent restatement (torch-CPU, tests/test_oracle.py) and by the golden
-fixtures it generated itself (tests/golden/, script tests/golden/make_golden.py).
+PINNED TO THE REFERENCE'S PROGRAM: the reference's own tests pin only shapes and
+parameter-leaf counts (encoders_test.py:170, models_test.py:52), JAX/Flax are not
+installed, no checkpoint is available offline and the reference ships no golden
+vectors.  Its unmodified layers.py / encoders.py / models.py are therefore executed
+in fp64 on NumPy stand-ins for jax / flax.linen / einshape (oracle/refshim,
+oracle/make_ref_fixtures.py) and their outputs recorded (tests/golden/ref_*.npz);
+tests/test_reference_program.py holds every function below against those records at
+1e-10.  Further pins: those structural facts, a second independent restatement
+(torch-CPU, tests/test_oracle.py) and the golden fixtures this module generated
+(tests/golden/make_golden.py).  Still unpinned: XLA's own arithmetic, bf16 dtype
+flow (mode 'bf16' is this module's emulation), the MLX path, any real checkpoint.
 """
 
 from __future__ import annotations
@@ -443,9 +447,10 @@ def softplus(x):
     return np.logaddexp(0.0, x)
 
 
-def atten_token_pooling(tokens, p, nm: Numerics, num_heads: int, hidden_dim: int):
+def atten_token_pooling(tokens, p, nm: Numerics, num_heads: int, hidden_dim: int, paddings=None):
     """layers.py:1044-1136 AttenTokenPoolingLayer(num_queries=1, add_layer_norm=True,
-    per-dim scale on, no logit cap, paddings None) -> [B, 1, D].
+    per-dim scale on, no logit cap) -> [B, 1, D].  `paddings` [B, T] (1 = padded token) masks keys
+    as layers.py:1106 does; the models call it with None.
 
     q = query param projected to [N, dh] (dh = hidden_dim / N) and scaled by
     1.442695041/sqrt(dh) * softplus(per_dim_scale) (layers.py:502-527); K, V projections of
@@ -465,7 +470,10 @@ def atten_token_pooling(tokens, p, nm: Numerics, num_heads: int, hidden_dim: int
     kt = np.transpose(k, (0, 2, 3, 1))
     logits = nm.act(np.matmul(qt, kt))
     sm_dt = np.float64 if nm.mode in ("f64", "wbf16") else np.float32
-    probs = nm.act(softmax(logits.astype(sm_dt)))
+    logits = logits.astype(sm_dt)
+    if paddings is not None:
+        logits = apply_mask_to_logits(logits, padding_mask(np.asarray(paddings))).astype(sm_dt)
+    probs = nm.act(softmax(logits))
     enc = nm.act(np.matmul(probs, np.transpose(v, (0, 2, 1, 3))))
     enc = np.transpose(enc, (0, 2, 1, 3))                                       # [B,1,N,dh]
     out = attention_projection_out(enc, pa["post"]["w"], pa["post"]["b"], nm)   # [B,1,D]

@@ -1,10 +1,12 @@
 """Generates the committed golden fixtures from the NumPy oracle (oracle/videoprism_oracle.py).
 
-PARITY UNPINNED by the reference: its tests hold no value-level vectors for this path
-(SURVEY.md §8(c)), JAX is not installed here, so these fixtures pin the oracle against
-future drift and give the GPU tests fixed vectors; their cross-check is the independent
-torch restatement (tests/torch_restatement.py) and the structural pins of the reference
-tests.  Run:  python tests/golden/make_golden.py
+The reference's tests hold no value-level vectors for this path and JAX is
+not installed here, so these fixtures pin the oracle against future drift and give the GPU
+tests fixed vectors.  The oracle itself is pinned to the reference's own program, executed in
+fp64 on NumPy stand-ins (oracle/make_ref_fixtures.py -> ref_*.npz, tests/test_reference_program.py),
+to the independent torch restatement (tests/torch_restatement.py) and to the structural pins of
+the reference tests.  Still unpinned: XLA's own arithmetic, bf16 dtype flow, the MLX path and any
+real checkpoint.  Run:  python tests/golden/make_golden.py
 """
 import os
 import sys

@@ -51,3 +51,29 @@ def test_classifier_large_u8(cuda):
     err = np.abs(logits - ref).max()
     print(f"classifier Large u8 f32: logits max-abs {err:.3e}")
     assert err < 2e-5
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+def test_classifier_vs_reference_program(cuda, bf16):
+    """The reference's own program as the yardstick (tests/golden/ref_base_classifier.npz: its
+    FactorizedVideoClassifier run in float64 on the NumPy stand-ins, oracle/make_ref_fixtures.py): Base widths, 1 + 1
+    layers, 40 classes, B = 2, T = 3, 72 x 72, one padded frame.  Bars: test_classifier_reduced_depth's."""
+    from ref_fixtures import Case
+    c = Case("ref_base_classifier", "base_classifier")
+    enc = {k: v for k, v in c.cfg.items() if k != "num_classes"}
+    m = models.get_model(None, model_fn=lambda: encoders.FactorizedVideoClassifier(encoder_params=enc,
+                                                                                  num_classes=c.cfg["num_classes"]),
+                         fprop_dtype=torch.bfloat16 if bf16 else None)
+    var = c.seeded_variables(m.param_specs())
+    logits, out = m.apply(var, c.video, return_intermediate=("global_embeddings",),
+                          frame_paddings=c.inp["frame_paddings"].astype(np.float32))
+    plain, _ = m.apply(var, c.video)
+    ref, rg = c.out["out_padded/0"], c.out["out_padded/1/global_embeddings"]
+    el, ep = np.abs(logits - ref).max(), np.abs(plain - c.out["out/0"]).max()
+    eg = np.abs(orc.l2_normalize(out["global_embeddings"]) - orc.l2_normalize(rg)).max()
+    print(f"classifier {'bf16' if bf16 else 'f32'} vs reference program: logits max-abs {el:.3e} (without paddings "
+          f"{ep:.3e}; |logits| max {np.abs(ref).max():.2f}), normalised global embedding {eg:.3e}")
+    if bf16:
+        assert el < 3e-2 and ep < 3e-2 and eg < 1e-3
+    else:
+        assert el < 2e-5 and ep < 2e-5 and np.abs(out["global_embeddings"] - rg).max() < 2e-5

@@ -227,3 +227,28 @@ def test_clip_large_dims_padded_frames(cuda, bf16):
     print(f"LvT-L dims {'bf16' if bf16 else 'f32'}: video {ev:.3e} frames {ef:.3e} text {et:.3e}")
     tol = 2e-3 if bf16 else 2e-5   # bf16 outputs are returned in bf16 (2^-9 relative)
     assert ev <= tol and ef <= tol and et <= tol, (ev, ef, et)
+
+
+@pytest.mark.parametrize("bf16", [False, True])
+def test_clip_vs_reference_program(cuda, bf16):
+    """The reference's own program as the yardstick (tests/golden/ref_base_lvt.npz: its FactorizedVideoCLIP run in
+    float64 on the NumPy stand-ins, oracle/make_ref_fixtures.py): LvT-Base widths, 1 + 1 vision, 1 auxiliary and 2
+    text layers, B = 2, T = 3, 72 x 72, one padded frame, texts of 12, 7 and 3 tokens.  Bars: test_clip_reduced_depth's,
+    2e-5 (fp32) and 1e-3 (bf16) on the L2-normalised embeddings."""
+    from ref_fixtures import Case
+    c = Case("ref_base_lvt", "base_lvt")
+    cfg = c.cfg
+    var = c.seeded_variables(params.clip_leaf_specs(cfg))
+    m = models.get_model(None, model_fn=lambda: encoders.FactorizedVideoCLIP(**cfg),
+                         fprop_dtype=torch.bfloat16 if bf16 else None)
+    ids, pads = c.inp["text_token_ids"], c.inp["text_paddings"].astype(np.float32)
+    v, t, out = m.apply(var, c.video, ids, pads, frame_paddings=c.inp["frame_paddings"].astype(np.float32),
+                        return_intermediate=("frame_embeddings",))
+    vp, _, _ = m.apply(var, c.video)
+    ev, et = np.abs(v - c.out["out_padded/0"]).max(), np.abs(t - c.out["out_padded/1"]).max()
+    ef = np.abs(out["frame_embeddings"] - c.out["out_padded/2/frame_embeddings"]).max()
+    ep = np.abs(vp - c.out["out/0"]).max()
+    print(f"clip {'bf16' if bf16 else 'f32'} vs reference program: video {ev:.3e} frames {ef:.3e} text {et:.3e} "
+          f"video without paddings {ep:.3e}")
+    tol = 1e-3 if bf16 else 2e-5
+    assert ev <= tol and ef <= tol and et <= tol and ep <= tol, (ev, ef, et, ep)

@@ -191,3 +191,33 @@ def test_temporal_attention_fused_vs_unfused_and_oracle(cuda, base):
     d = np.abs(fused - unfused)
     print(f"fused vs unfused: max-abs {d.max():.3e} mean-abs {d.mean():.3e}")
     assert d.mean() <= 5e-3
+
+
+def test_base_dims_vs_reference_program(cuda):
+    """The reference's own program as the yardstick (tests/golden/ref_base_encoder.npz: its FactorizedEncoder run
+    in float64 on the NumPy stand-ins, oracle/make_ref_fixtures.py): Base widths, 1 + 1 layers, B = 2, T = 3,
+    72 x 72 (both positional tables down-sampled, 16 x 16 -> 4 x 4 and 16 -> 3), one padded frame.  Bars: this
+    file's -- fp32 max-abs <= 1e-5; bf16 token mean-abs <= 2e-2 and the pooled L2 vector within 1e-3.  The record
+    holds every 2nd (padded run) / 4th (plain run) token row, every row's sum over the 768 columns (bar 768 x 1e-5,
+    what 1e-5 per element allows) and the mean over the tokens."""
+    from ref_fixtures import Case
+    c = Case("ref_base_encoder", "base_encoder")
+    cfg, var, video, fp = c.cfg, c.seeded_variables(), c.video, c.inp["frame_paddings"].astype(np.float32)
+    emb, out = _run(cfg, var, video, bf16=False, frame_paddings=fp, return_intermediate=True)
+    plain, _ = _run(cfg, var, video, bf16=False)
+    assert emb.shape == (2, 3 * 16, 768)
+    for key, got in (("out_padded/0", emb), ("out_padded/1/spatial_features", out["spatial_features"]),
+                     ("out/0", plain)):
+        for k, g, ref in c.records(key, got):
+            err = np.abs(g - ref).max()
+            print(f"f32 vs reference program {k}: max-abs {err:.3e}")
+            assert err <= (768 * 1e-5 if k.endswith("@rowsums") else 1e-5), (k, err)
+    for key, kw in (("out/0", {}), ("out_padded/0", dict(frame_paddings=fp))):
+        emb16, _ = _run(cfg, var, video, bf16=True, **kw)
+        rows, _, mean = c.records(key, emb16)
+        merr = np.abs(rows[1] - rows[2]).mean()
+        m, r = mean[1], mean[2]
+        perr = np.abs(m / np.sqrt((m * m).sum(-1, keepdims=True) + 1e-12) -
+                      r / np.sqrt((r * r).sum(-1, keepdims=True) + 1e-12)).max()
+        print(f"bf16 vs reference program {key}: token mean-abs {merr:.3e}; pooled-l2 max-abs {perr:.3e}")
+        assert merr <= 2e-2 and perr <= 1e-3

@@ -322,3 +322,23 @@ def test_giant_bf16_is_refused(cuda):
     flat = {k: torch.zeros(()).expand(*shape) for k, shape in mdl.param_specs().items()}
     with pytest.raises(NotImplementedError, match="dim_per_head"):
         mdl.apply(flat, _video(1, 2, 72, 0), train=False)
+
+
+def test_giant_dims_vs_reference_program(cuda):
+    """The reference's own program as the yardstick (tests/golden/ref_giant_encoder.npz: its FactorizedEncoder run
+    in float64 on the NumPy stand-ins, oracle/make_ref_fixtures.py): Giant widths, 1 + 1 layers, B = 2, T = 3,
+    72 x 72, one padded frame, spatial_features.  fp32 only (bf16 is refused at 88-wide heads); this file's bar,
+    max-abs <= 1e-5, on the recorded token rows and token means, 1408 x 1e-5 on the sums of the rows."""
+    from ref_fixtures import Case
+    c = Case("ref_giant_encoder", "giant_encoder")
+    cfg, var, video, fp = c.cfg, c.seeded_variables(), c.video, c.inp["frame_paddings"].astype(np.float32)
+    mdl = models.get_model(None, model_fn=lambda: models.encoders.FactorizedEncoder(**cfg))
+    emb, out = mdl.apply(var, video, train=False, frame_paddings=fp, return_intermediate=True)
+    plain, _ = mdl.apply(var, video, train=False)
+    assert emb.shape == (2, 3 * 16, 1408)
+    for key, got in (("out_padded/0", emb), ("out_padded/1/spatial_features", out["spatial_features"]),
+                     ("out/0", plain)):
+        for k, g, ref in c.records(key, got):
+            err = np.abs(g - ref).max()
+            print(f"f32 giant-dims vs reference program {k}: max-abs {err:.3e}")
+            assert err <= (1408 * 1e-5 if k.endswith("@rowsums") else 1e-5), (k, err)

@@ -1,7 +1,9 @@
 """CPU tests of the NumPy oracle: structural pins from the reference's own tests, the
 reference's own patchify call (einops, encoders.py:95-103), the committed golden fixtures,
-and an independent torch-CPU restatement.  Parity against JAX itself is unpinned (JAX is
-absent)."""
+and an independent torch-CPU restatement.  The reference's own program, executed in fp64 on
+NumPy stand-ins for jax / flax, pins the oracle in tests/test_reference_program.py; XLA's own
+arithmetic, bf16 dtype flow, the MLX path and any real checkpoint stay unpinned (JAX is absent;
+SURVEY.md §8(c))."""
 
 import os
 
