@@ -363,6 +363,54 @@ int vp_classifier_forward_windows(vp_classifier* c, const void* states, int64_t 
                                   float* logits, float* embeddings, void* spatial_out, void* spatiotemporal_out,
                                   int out_dtype, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---------------- training the classifier's head on frozen tokens ----------------
+ * The head of FactorizedVideoClassifier (encoders.py:634-652: atten_pooler, then projection) has no released
+ * weights; VideoPrism is evaluated with a frozen backbone and a trained attentive probe.  These stateless ops are
+ * the head's forward and backward over tokens [B, S, D] (the encoder's 'spatiotemporal_features', VP_F32 or
+ * VP_BF16) that take no gradient.  Parameters and gradients are DEVICE fp32 arrays in the reference's own layouts;
+ * dims: model_dim % 128 == 0, at most 1536, a multiple of num_heads <= 16 (else VP_ENOTSUP).  The calls are
+ * asynchronous on `stream` on the current device, never allocate and never synchronise.
+ *   vp_op_probe_forward   logits [B, C] fp32; emb [B, D] fp32 (the pooled embedding) or NULL.  Leaves in `ws` what
+ *                         the backward needs.
+ *   vp_op_probe_backward  dlogits [B, C] fp32 -> every member of `grads` (all required; key_b's gradient is
+ *                         exactly zero: the key bias cancels in the softmax).  `ws` is the workspace the forward
+ *                         of the same params, tokens, B and S filled; it may be called more than once on it.
+ * Equal inputs give equal bits: no sum is formed with atomics.  The tokens are read twice by each call. */
+typedef struct vp_probe_dims {
+  int32_t model_dim;   /* D */
+  int32_t num_heads;   /* H; dim_per_head dh = D / H */
+  int32_t num_classes; /* C */
+} vp_probe_dims;
+
+typedef struct vp_probe_params {           /* leaf under 'params' */
+  const float* query;                      /* atten_pooler/pooling_attention_query [1, D] */
+  const float* per_dim_scale;              /* atten_pooler/pooling_attention/per_dim_scale/per_dim_scale [dh] */
+  const float *query_w, *query_b;          /* .../pooling_attention/query/{w [D, H, dh], b [H, dh]} */
+  const float *key_w, *key_b;              /* .../key/{w, b} */
+  const float *value_w, *value_b;          /* .../value/{w, b} */
+  const float *post_w, *post_b;            /* .../post/{w [D, H, dh], b [D]} */
+  const float *ln_scale, *ln_bias;         /* atten_pooler/pooling_attention_layer_norm/{scale, bias} [D] */
+  const float *proj_kernel, *proj_bias;    /* projection/linear/{kernel [D, C], bias [C]} */
+} vp_probe_params;
+
+typedef struct vp_probe_grads { /* member for member the gradient of vp_probe_params, same shapes */
+  float* query;
+  float* per_dim_scale;
+  float *query_w, *query_b;
+  float *key_w, *key_b;
+  float *value_w, *value_b;
+  float *post_w, *post_b;
+  float *ln_scale, *ln_bias;
+  float *proj_kernel, *proj_bias;
+} vp_probe_grads;
+
+int vp_op_probe_workspace_bytes(const vp_probe_dims* dims, int64_t B, int64_t S, size_t* bytes);
+int vp_op_probe_forward(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens, int dtype,
+                        int64_t B, int64_t S, float* logits, float* emb, void* ws, size_t ws_bytes, void* stream);
+int vp_op_probe_backward(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens, int dtype,
+                         int64_t B, int64_t S, const float* dlogits, const vp_probe_grads* grads, void* ws,
+                         size_t ws_bytes, void* stream);
+
 /* ---------------- multi-GPU: RCCL all-gather of pooled clip embeddings ----------------
  * The reference runs on one device; its video-text usage scores every clip against every query,
  * `similarities = video_emb @ text_emb.T` (README.md:81, verify_clip_models.py:84).  With clips

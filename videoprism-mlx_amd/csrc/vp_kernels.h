@@ -232,6 +232,42 @@ hipError_t similarity(const float* a, const float* b, int B, int Q, int D, float
 
 hipError_t pool_l2(const void* emb, int is_bf16, int B, int L, int D, float* out, hipStream_t s);
 
+// ---- training the classifier head on frozen tokens (probe_kernels.hip; H heads of dh = D / H) ----
+// qraw [H][dh] (= query . Wq on entry) += bq, q~ = qraw * 1.442695041/sqrt(dh) * softplus(pds), U [H][D] = Wk[:,h,:] q~[h];
+// split (bf16 tokens): Ut [32][D] = (U_hi | U_lo | 0) as well, and U = U_hi + U_lo
+hipError_t probe_fold(float* qraw, const float* bq, const float* pds, const float* Wk, int D, int H, int split,
+                      float* qt, float* U, bf16_t* Ut, hipStream_t s);
+// wvt [H][D][dh] and wpt [H*dh][D] from the reference's [D][H][dh] leaves (small_gemm's operands), gamma = 1 + scale
+hipError_t probe_pack(const float* wv, const float* wp, const float* scale, int D, int H, float* wvt, float* wpt,
+                      float* gamma, hipStream_t s);
+// out[z][m * ldo + n] = sum_k A[z][m * am + k * ak] * Bm[z][k * bk + n] over `batch` matrices at element strides
+// sA / sB / sO (products and sums over b of outer products of the backward); probe_dot: the same with both
+// operands contiguous in k, out[z][m * ldo + n] = A[z][m * am + :] . Bm[z][n * bn + :]
+hipError_t probe_gemm(const float* A, int64_t sA, int64_t am, int64_t ak, const float* Bm, int64_t sB, int64_t bk,
+                      float* out, int64_t sO, int64_t ldo, int M, int N, int K, int batch, hipStream_t s);
+hipError_t probe_dot(const float* A, int64_t sA, int64_t am, const float* Bm, int64_t sB, int64_t bn, float* out,
+                     int64_t sO, int64_t ldo, int M, int N, int K, int batch, hipStream_t s);
+// out[n] = sum_m x[m][n]
+hipError_t probe_colsum(const float* x, int M, int N, float* out, hipStream_t s);
+// LayerNorm backward over rows of x [rows][D]: dx, stats [rows][2] = (mean, rstd), dscale / dbias [D]
+hipError_t probe_ln_bwd(const float* x, const float* dy, const float* gamma, int rows, int D, float* dx, float* stats,
+                        float* dscale, float* dbias, hipStream_t s);
+// r [B][H] = z . dz; split: dzt [B][32][D] = (dz_hi | dz_lo | 0) per clip and dz = dz_hi + dz_lo in place
+hipError_t probe_dz_finish(const float* z, float* dz, int B, int H, int D, int split, bf16_t* dzt, float* r,
+                           hipStream_t s);
+// pass 1: dl [B][H][S] = p (x . dz - r), p from the forward's logits and stats (bf16 x with S % 32 == 0 and dzt:
+// the MFMA kernel); pass 2: dU [H][D] = sum_{b,s} dl x through part [B][pool_chunks(S)][H][D] and dUclip [B][H][D]
+bool probe_dl_uses_mfma(int in_bf16, int S);
+hipError_t probe_dl(const void* x, int in_bf16, int B, int S, int D, int H, const float* dz, const bf16_t* dzt,
+                    const float* logits, const float* stats, const float* r, float* dl, hipStream_t s);
+hipError_t probe_wsum(const void* x, int in_bf16, int B, int S, int D, int H, const float* dl, float* part,
+                      float* dUclip, float* dU, hipStream_t s);
+// dwk [D][H][dh] = dU[h][d] q~[h][j]
+hipError_t probe_fold_bwd(const float* dU, const float* qt, int D, int H, float* dwk, hipStream_t s);
+// dqraw [H][dh] = dq~ c softplus(pds), dpds [dh] = c sigmoid(pds) sum_h dq~ qraw
+hipError_t probe_dq(const float* dqt, const float* qraw, const float* pds, int D, int H, float* dqraw, float* dpds,
+                    hipStream_t s);
+
 // ---- frame ingest (preprocess.hip) ----
 // video_utils.py:109-124: size of the resized frame and the crop window's origin in it (mode 0 centre
 // crop, 1 stretch to S x S); a message if this library's kernel cannot take the geometry, else nullptr

@@ -67,6 +67,33 @@ class vp_clip_config(ctypes.Structure):
 NORM_POLICIES = {"pre": 0, "primer_hybrid": 1}
 
 
+class vp_probe_dims(ctypes.Structure):
+    _fields_ = [("model_dim", c_int32), ("num_heads", c_int32), ("num_classes", c_int32)]
+
+
+# members of vp_probe_params / vp_probe_grads, in order, and the leaf each one is (path under 'params')
+PROBE_LEAVES = (
+    ("query", "atten_pooler/pooling_attention_query"),
+    ("per_dim_scale", "atten_pooler/pooling_attention/per_dim_scale/per_dim_scale"),
+    ("query_w", "atten_pooler/pooling_attention/query/w"),
+    ("query_b", "atten_pooler/pooling_attention/query/b"),
+    ("key_w", "atten_pooler/pooling_attention/key/w"),
+    ("key_b", "atten_pooler/pooling_attention/key/b"),
+    ("value_w", "atten_pooler/pooling_attention/value/w"),
+    ("value_b", "atten_pooler/pooling_attention/value/b"),
+    ("post_w", "atten_pooler/pooling_attention/post/w"),
+    ("post_b", "atten_pooler/pooling_attention/post/b"),
+    ("ln_scale", "atten_pooler/pooling_attention_layer_norm/scale"),
+    ("ln_bias", "atten_pooler/pooling_attention_layer_norm/bias"),
+    ("proj_kernel", "projection/linear/kernel"),
+    ("proj_bias", "projection/linear/bias"),
+)
+
+
+class vp_probe_params(ctypes.Structure):  # device fp32 pointers; vp_probe_grads has the same members
+    _fields_ = [(member, c_void_p) for member, _ in PROBE_LEAVES]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "vp_last_error": (c_char_p, []),
@@ -166,6 +193,15 @@ _SIGNATURES = {
     "vp_clip_text_workspace_bytes": (c_int, [c_void_p, c_int64, c_int64, POINTER(c_size_t)]),
     "vp_clip_encode_text": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
+    # the classifier head's training ops over frozen tokens (videoprism/probe.py)
+    "vp_op_probe_workspace_bytes": (c_int, [POINTER(vp_probe_dims), c_int64, c_int64, POINTER(c_size_t)]),
+    "vp_op_probe_forward": (c_int, [POINTER(vp_probe_dims), POINTER(vp_probe_params), c_void_p, c_int, c_int64,
+                                    c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_op_probe_backward": (c_int, [POINTER(vp_probe_dims), POINTER(vp_probe_params), c_void_p, c_int, c_int64,
+                                     c_int64, c_void_p, POINTER(vp_probe_params), c_void_p, c_size_t, c_void_p]),
+    # not in the public header: one streaming pass of the backward on its own (tools/probe_bench.py)
+    "vp_dev_probe_backward_pass": (c_int, [POINTER(vp_probe_dims), c_void_p, c_int, c_int64, c_int64, c_int, c_void_p,
+                                           c_size_t, c_void_p]),
     # not in the public header: named-kernel GEMM for A/B tests and tools/gemm_bench.py
     "vp_dev_gemm_kernel": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
@@ -506,6 +542,54 @@ def dev_pooler(kind, handle, feat, G, S, do_l2, dst, scratch, stream=None):
     call("vp_dev_pooler", kind, handle, _ptr(feat), G, S, 1 if do_l2 else 0, _ptr(dst), _ptr(scratch),
          ctypes.byref(n), _stream(stream))
     return dst
+
+
+# The classifier head's training ops.  `tensors`: {member of vp_probe_params: contiguous fp32 tensor on the
+# tokens' device}, the parameters or, for the backward, the gradients to fill.
+def _probe_struct(tensors):
+    return vp_probe_params(**{member: _ptr(tensors[member]) for member, _ in PROBE_LEAVES})
+
+
+def op_probe_workspace_bytes(model_dim, num_heads, num_classes, B, S) -> int:
+    dims = vp_probe_dims(model_dim, num_heads, num_classes)
+    n = c_size_t()
+    call("vp_op_probe_workspace_bytes", ctypes.byref(dims), B, S, ctypes.byref(n))
+    return n.value
+
+
+def op_probe_forward(dims, tensors, tokens, logits, emb, ws, ws_bytes=None, stream=None):
+    """logits [B, C] (and emb [B, D] unless None) of the head over tokens [B, S, D]; fills the workspace `ws`
+    (uint8, op_probe_workspace_bytes) with what op_probe_backward needs."""
+    import torch
+    B, S, _ = tokens.shape
+    d = vp_probe_dims(*dims)
+    with torch.cuda.device(tokens.device):  # no handle: the ops launch on the current device
+        call("vp_op_probe_forward", ctypes.byref(d), ctypes.byref(_probe_struct(tensors)), _ptr(tokens), _prec(tokens),
+             B, S, _ptr(logits), _ptr(emb), _ptr(ws), ws.numel() if ws_bytes is None else ws_bytes, _stream(stream))
+    return logits
+
+
+def op_probe_backward(dims, tensors, tokens, dlogits, grads, ws, ws_bytes=None, stream=None):
+    """Fills `grads` (same members as `tensors`) from dlogits [B, C] and the workspace the forward filled."""
+    import torch
+    B, S, _ = tokens.shape
+    d = vp_probe_dims(*dims)
+    with torch.cuda.device(tokens.device):
+        call("vp_op_probe_backward", ctypes.byref(d), ctypes.byref(_probe_struct(tensors)), _ptr(tokens),
+             _prec(tokens), B, S, _ptr(dlogits), ctypes.byref(_probe_struct(grads)), _ptr(ws),
+             ws.numel() if ws_bytes is None else ws_bytes, _stream(stream))
+    return grads
+
+
+def dev_probe_backward_pass(dims, tokens, which, ws, stream=None):
+    """Pass 1 (which 1: dl from the tokens) or pass 2 (which 2: dU) of the backward alone, on a workspace
+    op_probe_backward has run on; for timing."""
+    import torch
+    B, S, _ = tokens.shape
+    d = vp_probe_dims(*dims)
+    with torch.cuda.device(tokens.device):
+        call("vp_dev_probe_backward_pass", ctypes.byref(d), _ptr(tokens), _prec(tokens), B, S, which, _ptr(ws),
+             ws.numel(), _stream(stream))
 
 
 # vp_dev_attention_choice: stack kinds (vp_internal.h AttnKind; ATT_OP: as vp_op_attention maps S and the key
