@@ -161,5 +161,99 @@ def attention(other):
             f"{k} {min(v)*1e3:7.1f} us" for k, v in res.items()), flush=True)
 
 
+def pooler(other, control=False):
+    """The pooler's streaming passes one at a time (vp_dev_pool_logits, vp_dev_pool_softmax_wsum; the *_wide entry
+    where the plain one refuses the width) and the head's training ops (vp_op_probe_forward, then
+    vp_op_probe_backward: the logits and all 14 gradients) at the first five shapes of tests/test_gpu_probe.py and at
+    Base's head shape.  Bitwise this vs other; interleaved timing with the other library loaded a second time, so
+    other vs other2 is the run's own spread, and `over` is min(this) - min(other) set against it.  A third argument
+    `control` runs the same with a copy of the other library in this tree's place."""
+    from videoprism.probe import AttentiveProbe
+    dev = torch.device("cuda:0")
+    if control:  # a copy of the other library stands in for this tree's: what the harness itself adds to "this"
+        nat._LIB_PATH = tempfile.NamedTemporaryFile(suffix=".so", delete=False).name
+        shutil.copy(other, nat._LIB_PATH)
+    tmp = tempfile.NamedTemporaryFile(suffix=".so", delete=False).name
+    shutil.copy(other, tmp)
+    libs = {"this": nat.load(), "other": ctypes.CDLL(other), "other2": ctypes.CDLL(tmp)}
+    os.unlink(tmp)
+    if control:
+        os.unlink(nat._LIB_PATH)
+    names = ("vp_dev_pool_logits", "vp_dev_pool_logits_wide", "vp_dev_pool_softmax_wsum",
+             "vp_dev_pool_softmax_wsum_wide", "vp_op_probe_forward", "vp_op_probe_backward")
+    for lib in libs.values():
+        for name in names:
+            f = getattr(lib, name)
+            f.restype, f.argtypes = nat._SIGNATURES[name]
+    st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+    def ab(label, run, outs):
+        """run(k) fills outs[k] (a list of tensors) through library k."""
+        for k in libs:
+            run(k)
+        torch.cuda.synchronize()
+        same = all(torch.equal(a, b) for a, b in zip(outs["this"], outs["other"]))
+        res = {k: [] for k in libs}
+        for _ in range(5):
+            for k in libs:
+                res[k].append(timeit(lambda k=k: run(k)))
+        t = {k: min(v) * 1e3 for k, v in res.items()}
+        over, spread = t["this"] - t["other"], abs(t["other"] - t["other2"])
+        print(f"{label}: bitwise this == other {same}; " + " | ".join(f"{k} {v:8.1f} us" for k, v in t.items()) +
+              f" | over {over:+7.1f} us, spread {spread:6.1f} us: {'within' if over <= spread else 'OUTSIDE'}",
+              flush=True)
+
+    cases = [(False, 1, 40, 128, 2, 1), (False, 3, 300, 384, 6, 5), (False, 2, 257, 1408, 16, 70),
+             (True, 2, 512, 256, 4, 3), (True, 3, 300, 384, 6, 5), (True, 32, 4096, 768, 12, 400)]
+    for bf16, B, S, D, H, C in cases:
+        shape = f"{'bf16' if bf16 else 'fp32'} B={B} S={S} D={D} H={H}"
+        g = torch.Generator(device=dev).manual_seed(1000 * D + 10 * S + B)
+        x = torch.randn((B * S, D), generator=g, device=dev).to(torch.bfloat16 if bf16 else torch.float32)
+        U = torch.randn((H, D), generator=g, device=dev) / D ** 0.5
+        Ut = torch.from_numpy(nat.dev_pool_split_u(U.cpu().numpy()).view("int16")).to(dev) if bf16 else None
+        dt = nat._prec(x)
+        lg = {k: [torch.full((B, H, S), -1.0, device=dev)] for k in libs}
+        fn = "vp_dev_pool_logits" + ("_wide" if D > 1024 else "")
+        ab(f"pool_logits {shape}", lambda k: _ok(getattr(libs[k], fn)(ptr(x), dt, B * S, S, D, ptr(U), ptr(Ut), H,
+                                                                       ptr(lg[k][0]), st())), lg)
+        Cn = nat.dev_pool_chunks(S)
+        zs = {k: [torch.full((B * H, 2), -1.0, device=dev), torch.full((B, Cn, H, D), -1.0, device=dev),
+                  torch.full((B, H, D), -1.0, device=dev)] for k in libs}
+        fn2 = "vp_dev_pool_softmax_wsum" + ("_wide" if D > 1024 or D % 256 else "")
+        ab(f"pool_softmax_wsum {shape}",
+           lambda k: _ok(getattr(libs[k], fn2)(ptr(x), dt, B, S, D, H, ptr(lg["this"][0]), ptr(zs[k][0]), ptr(zs[k][1]),
+                                               ptr(zs[k][2]), st())), zs)
+
+        probe = AttentiveProbe(D, H, C, device=dev, seed=0)
+        tensors = {m: probe.get_parameter(path).detach() for m, path in nat.PROBE_LEAVES}
+        dims, params = nat.vp_probe_dims(D, H, C), nat._probe_struct(tensors)
+        dlogits = torch.randn((B, C), generator=g, device=dev)
+        need = nat.op_probe_workspace_bytes(D, H, C, B, S)
+        ws = {k: torch.empty(need, dtype=torch.uint8, device=dev) for k in libs}
+        out = {k: [torch.full((B, C), -1.0, device=dev)] + [torch.full_like(tensors[m], -1.0) for m, _ in nat.PROBE_LEAVES]
+               for k in libs}
+        gr = {k: nat._probe_struct(dict(zip((m for m, _ in nat.PROBE_LEAVES), out[k][1:]))) for k in libs}
+
+        def fwd(k):
+            _ok(libs[k].vp_op_probe_forward(ctypes.byref(dims), ctypes.byref(params), ptr(x), dt, B, S, ptr(out[k][0]),
+                                            None, ptr(ws[k]), need, st()))
+
+        def both(k):
+            fwd(k)
+            _ok(libs[k].vp_op_probe_backward(ctypes.byref(dims), ctypes.byref(params), ptr(x), dt, B, S, ptr(dlogits),
+                                             ctypes.byref(gr[k]), ptr(ws[k]), need, st()))
+        both("this")  # every gradient written before the forward-only comparison reads the lists
+        ab(f"probe forward+backward {shape}", both, out)
+        ab(f"probe forward {shape}", fwd, out)
+
+
+def _ok(rc):
+    assert rc == 0, nat.load().vp_last_error()
+
+
 if __name__ == "__main__":
-    {"tattn": tattn, "spatial": spatial, "attention": attention}[sys.argv[1]](sys.argv[2])
+    if sys.argv[1] == "pooler":
+        pooler(sys.argv[2], control=sys.argv[3:] == ["control"])
+    else:
+        {"tattn": tattn, "spatial": spatial, "attention": attention}[sys.argv[1]](sys.argv[2])

@@ -2,7 +2,9 @@
 IDENT where a kernel's instruction stream is the same text (comments and the function's index in basic-block labels
 aside), else DIFF with both VGPR counts, instruction counts, scratch sizes and spill counts.  A refactor that must not move a kernel checks it with this.
 
-  python tools/asm_identity.py OLD.s NEW.s
+  python tools/asm_identity.py OLD.s NEW.s [OLDNAME=NEWNAME ...]
+
+A kernel that the refactor renamed is matched by naming the pair: the old listing's OLDNAME is compared as NEWNAME.
 """
 import re
 import shutil
@@ -19,7 +21,8 @@ def kernels(path):
         a = next(i for i, l in enumerate(lines) if l.startswith(sym + ":"))
         b = next(i for i in range(a, len(lines)) if lines[i].startswith(".Lfunc_end"))
         # (basic-block labels carry the function's index in the listing, which moves with the order of instantiation)
-        body = [re.sub(r"BB\d+_", "BB_", l) for l in lines[a + 1:b] if "__hip_cuid" not in l]
+        # (... and the directives inside the body name the kernel itself, which a rename changes)
+        body = [re.sub(r"BB\d+_", "BB_", l).replace(sym, "<kernel>") for l in lines[a + 1:b] if "__hip_cuid" not in l]
         res_spills = sum("Spill" in l for l in body)
         body = [l for l in (re.sub(r"\s*;.*$", "", l) for l in body) if l]  # no comments
         tail = "\n".join(lines[b:b + 40])
@@ -36,6 +39,9 @@ def kernels(path):
 
 if __name__ == "__main__":
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    for pair in sys.argv[3:]:  # OLD=NEW: the old listing's kernels whose name contains OLD are compared as NEW
+        a, b = pair.split("=")
+        old = {k.replace(a, b): v for k, v in old.items()}
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:
             print("ONLY-%s %s" % ("OLD" if name in old else "NEW", name))

@@ -10,131 +10,39 @@
 //   z[g,h,:]   = sum_s p[g,h,s] x[g,s,:]
 // which turns the two [S x D] x [D x 4D] projections per clip into two streaming passes over x
 // (HBM-bound: pool_logits, pool_wsum) and [G x D] x [D x dh] matrix products (small_gemm).
-//   pool_logits : logits[g][h][s] = x[g*S+s] . U[h]       (bf16: skinny MFMA GEMM; fp32: U in LDS)
+//   pool_logits : logits[g][h][s] = x[g*S+s] . U[h]       (pool_stream.h pass 1, U shared by all clips)
 //   pool_stats  : (max, 1/sum exp(l - max)) per (g, h)    (fp32 softmax, layers.py:650-654)
-//   pool_wsum   : zpart[g][c][h][:] = sum over the c-th 256-row chunk of p * x
+//   pool_wsum   : zpart[g][c][h][:] = sum over the c-th 256-row chunk of p * x   (pool_stream.h pass 2)
 //   pool_reduce : z[g][h][:] = sum_c zpart
 //   small_gemm  : out[m][n] = A[m][:] . Wt[:][n] + bias[n], batched (enc per head, then post)
 //   ln_l2_rows  : LayerNorm (layers.py:208-270) and/or _l2_normalize (encoders.py:50-67), fp32
-// Widths: D up to kPoolMaxD = 1536 (LayerNorm's range; Giant is 1408 = 22 x 64 = 5 x 256 + 128).  pool_logits takes
-// D = 64 k, with U for all heads in LDS (more than 64 KB past D = 1024 at 16 heads: the launcher opts in);
-// pool_wsum takes D = 128 k, the odd k with a 128-wide last column block; ln_l2_rows any D up to the limit.  Every
-// width up to 1024 runs the instantiation, grid and summation order it always ran.
+// Widths: D up to kPoolMaxD = 1536 (LayerNorm's range; Giant is 1408 = 22 x 64 = 5 x 256 + 128), at most kPoolMaxH
+// heads.  The passes' own width rules are pool_stream.h's; ln_l2_rows takes any D up to the limit.  Every width up
+// to 1024 runs the instantiation, grid and summation order it always ran.
 // Text tower: text_embed = Embedding(ids)*sqrt(D) + sinusoidal PositionalEmbedding, with the
 // CLS token appended (encoders.py:190-266, :700-740).  similarity = video_emb . text_emb^T.
-#include "vp_common.h"
-#include "vp_kernels.h"
+#include "pool_stream.h"
 
 namespace vp {
 
 namespace {
 
-__device__ __forceinline__ float ldx(const void* p, int in_bf16, int64_t i) {
-  return in_bf16 ? bf2f(static_cast<const bf16_t*>(p)[i]) : static_cast<const float*>(p)[i];
-}
+struct StoreLogits {
+  float* __restrict__ logits;
+  __device__ __forceinline__ void operator()(int64_t, int64_t idx, float v) const { logits[idx] = v; }
+};
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-// block (256 threads) reductions through LDS
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
-
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-constexpr int kPlRows = 64;  // rows per workgroup (16 per wave)
-
-// NJ: 64-column steps a lane keeps in registers: 16 (D <= 1024, the kernel every width up to Large runs) or 24
-// (D <= 1536; 22 steps at Giant's 1408).  U [H][D] sits in dynamic LDS whole: past 64 KB (16 heads x 1408 columns
-// are 90,112 B) the launcher opts in to the larger allocation, as the 88-wide fp32 attention kernel does.
 template <int NJ>
 __global__ __launch_bounds__(256) void pool_logits_kernel(const void* __restrict__ x, int in_bf16, int64_t rows,
                                                           int S, int D, const float* __restrict__ U, int H,
                                                           float* __restrict__ logits) {
-  extern __shared__ float Us[];  // [H][D]
-  for (int i = threadIdx.x; i < H * D; i += 256) Us[i] = U[i];
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int nj = D >> 6;
-  for (int rr = 0; rr < kPlRows / 4; ++rr) {
-    const int64_t r = (int64_t)blockIdx.x * kPlRows + w * (kPlRows / 4) + rr;
-    if (r >= rows) break;  // uniform per wave
-    float xv[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) xv[j] = j < nj ? ldx(x, in_bf16, r * D + lane + 64 * j) : 0.0f;
-    const int64_t g = r / S, s = r % S;
-    for (int h = 0; h < H; ++h) {
-      float a = 0.0f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        if (j < nj) a = fmaf(xv[j], Us[h * D + lane + 64 * j], a);
-      a = wave_sum(a);
-      if (lane == 0) logits[(g * H + h) * S + s] = a;
-    }
-  }
+  pool_scalar_pass<NJ, false>(x, in_bf16, rows, S, D, U, H, StoreLogits{logits});
 }
 
-// bf16 tokens: logits as a skinny GEMM on v_mfma_f32_32x32x16_bf16.  One wave owns 32 rows;
-// the B operand is Ut [32][D] bf16 = (U_hi | U_lo | 0) with U = U_hi + U_lo split on the host, so
-// the fp32 U survives the bf16 operands to ~2^-16 relative; lane c < H adds column H + c.
 __global__ __launch_bounds__(256) void pool_logits_mfma_kernel(const bf16_t* __restrict__ x, int64_t rows, int S,
                                                                int D, const bf16_t* __restrict__ Ut, int H,
                                                                float* __restrict__ logits) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
-  if (r0 >= rows) return;  // whole wave
-  const int i = lane & 31, half = lane >> 5;
-  const bf16_t* ap = x + (r0 + i) * D + 8 * half;
-  const bf16_t* bp = Ut + (int64_t)i * D + 8 * half;
-  f32x16 acc = {};
-  const int nt = D >> 4;
-  int t = 0;
-  for (; t + 8 <= nt; t += 8) {
-    bf16x8 a[8], b[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      a[u] = *reinterpret_cast<const bf16x8*>(ap + 16 * (t + u));
-      b[u] = *reinterpret_cast<const bf16x8*>(bp + 16 * (t + u));
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u], b[u], acc, 0, 0, 0);
-  }
-  for (; t < nt; ++t) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(ap + 16 * t);
-    const bf16x8 b = *reinterpret_cast<const bf16x8*>(bp + 16 * t);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-  }
-  // acc[r] = C[row = (r&3) + 8(r>>2) + 4*half][col = i]
-  const int64_t g = r0 / S;
-  const int64_t s0 = r0 % S;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const float v = acc[r] + __shfl_down(acc[r], H);
-    if (i < H) logits[(g * H + i) * S + s0 + (r & 3) + 8 * (r >> 2) + 4 * half] = v;
-  }
+  pool_mfma_pass<false>(x, rows, S, D, Ut, H, StoreLogits{logits});
 }
 
 __global__ __launch_bounds__(256) void pool_stats_kernel(const float* __restrict__ logits, int S,
@@ -153,90 +61,34 @@ __global__ __launch_bounds__(256) void pool_stats_kernel(const float* __restrict
   }
 }
 
-constexpr int kPwRows = 256;  // rows per chunk
-constexpr int kPwMaxH = 16;
+// the softmax rebuilt from the logits and pool_stats, the [256][16] weights visited by row
+struct FillSoftmax {
+  static constexpr bool kByRow = true;
+  const float* __restrict__ logits;
+  const float* __restrict__ stats;
+  __device__ __forceinline__ float operator()(int64_t gh, int64_t idx) const {
+    return softmax_p(logits, stats, gh, idx);
+  }
+};
 
-// zpart[g][c][h][d] = sum over rows of chunk c of p[g,h,s] x[g*S+s][d]: a workgroup owns one
-// (g, 256-row chunk, 256-column block) with 128 threads; a thread owns two adjacent columns (one 4-byte
-// bf16 pair / 8-byte fp32 pair per row) and all 16 head sums of each, the probabilities of the chunk sit in
-// LDS (float4 broadcast reads).  Each column is summed over the rows in row order.  D = 128 k with k odd
-// (1408 = 5 x 256 + 128): the last column block is 128 wide, its second wave fills its share of the
-// probabilities and leaves, so no lane reads or writes a column past D and x is still read once.
 __global__ __launch_bounds__(128) void pool_wsum_kernel(const void* __restrict__ x, int in_bf16, int S, int D,
                                                         int H, const float* __restrict__ logits,
                                                         const float* __restrict__ stats, int C,
                                                         float* __restrict__ zpart) {
-  __shared__ __attribute__((aligned(16))) float ps[kPwRows][kPwMaxH];
-  const int nq = (D + 255) >> 8;
-  const int q = blockIdx.x % nq;
-  const int gc = blockIdx.x / nq;
-  const int g = gc / C;
-  const int c = gc % C;
-  const int r0 = c * kPwRows;
-  const int nr = S - r0 < kPwRows ? S - r0 : kPwRows;
-  for (int i = threadIdx.x; i < kPwRows * kPwMaxH; i += 128) {
-    const int r = i / kPwMaxH, h = i % kPwMaxH;
-    float p = 0.0f;
-    if (r < nr && h < H) {
-      const int64_t gh = (int64_t)g * H + h;
-      p = __expf(logits[gh * S + r0 + r] - stats[2 * gh]) * stats[2 * gh + 1];
-    }
-    ps[r][h] = p;
-  }
-  __syncthreads();
-  const int d = q * 256 + 2 * threadIdx.x;
-  if (d >= D) return;  // the half block's second wave, whole
-  float acc0[kPwMaxH], acc1[kPwMaxH];
-#pragma unroll
-  for (int h = 0; h < kPwMaxH; ++h) acc0[h] = acc1[h] = 0.0f;
-  const int64_t rowbase = (int64_t)g * S + r0;
-  auto ld2 = [&](int r) -> float2 {
-    const int64_t i = (rowbase + r) * D + d;
-    if (in_bf16) {
-      const uint32_t u = *reinterpret_cast<const uint32_t*>(static_cast<const bf16_t*>(x) + i);
-      return make_float2(__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u));
-    }
-    return *reinterpret_cast<const float2*>(static_cast<const float*>(x) + i);
-  };
-  auto row = [&](int r, float2 xv) {
-    const float4* pr = reinterpret_cast<const float4*>(ps[r]);
-#pragma unroll
-    for (int h4 = 0; h4 < kPwMaxH / 4; ++h4) {
-      const float4 p = pr[h4];
-      acc0[4 * h4] = fmaf(p.x, xv.x, acc0[4 * h4]);
-      acc0[4 * h4 + 1] = fmaf(p.y, xv.x, acc0[4 * h4 + 1]);
-      acc0[4 * h4 + 2] = fmaf(p.z, xv.x, acc0[4 * h4 + 2]);
-      acc0[4 * h4 + 3] = fmaf(p.w, xv.x, acc0[4 * h4 + 3]);
-      acc1[4 * h4] = fmaf(p.x, xv.y, acc1[4 * h4]);
-      acc1[4 * h4 + 1] = fmaf(p.y, xv.y, acc1[4 * h4 + 1]);
-      acc1[4 * h4 + 2] = fmaf(p.z, xv.y, acc1[4 * h4 + 2]);
-      acc1[4 * h4 + 3] = fmaf(p.w, xv.y, acc1[4 * h4 + 3]);
-    }
-  };
-  int r = 0;
-  for (; r + 16 <= nr; r += 16) {
-    float2 xv[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) xv[u] = ld2(r + u);
-#pragma unroll
-    for (int u = 0; u < 16; ++u) row(r + u, xv[u]);
-  }
-  for (; r < nr; ++r) row(r, ld2(r));
-  float* zp = zpart + ((int64_t)g * C + c) * H * D + d;
-#pragma unroll
-  for (int h = 0; h < kPwMaxH; ++h)
-    if (h < H) *reinterpret_cast<float2*>(zp + (int64_t)h * D) = make_float2(acc0[h], acc1[h]);
+  pool_wsum_pass(x, in_bf16, S, D, H, C, FillSoftmax{logits, stats}, zpart);
 }
 
-__global__ __launch_bounds__(256) void pool_reduce_kernel(const float* __restrict__ zpart, int C, int64_t HD,
-                                                          int64_t total, float* __restrict__ z) {
+// out[g][e] = sum_{i < n} part[g][i][e] in index order
+__global__ __launch_bounds__(256) void pool_reduce_kernel(const float* __restrict__ part, int n, int64_t HD,
+                                                          int64_t total, float* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int64_t g = i / HD, e = i % HD;
-  const float* p = zpart + g * C * HD + e;
+  const float* p = part + g * n * HD + e;
   float s = 0.0f;
-  for (int c = 0; c < C; ++c) s += p[(int64_t)c * HD];
-  z[i] = s;
+#pragma unroll 8
+  for (int c = 0; c < n; ++c) s += p[(int64_t)c * HD];
+  out[i] = s;
 }
 
 // out[m][n] = A[m][:] . Wt[:][n] + bias[n] for small M (pooled vectors): a workgroup owns 64
@@ -330,18 +182,8 @@ __global__ __launch_bounds__(256) void ln_l2_rows_kernel(const void* __restrict_
     v[j] = (j < nj && d < D) ? ldx(x, in_bf16, r * stride + d) : 0.0f;
   }
   if (gamma) {
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) s += v[j];
-    const float mean = block_sum(s, red) / (float)D;
-    float q = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-      const int d = threadIdx.x + 256 * j;
-      const float c = (j < nj && d < D) ? v[j] - mean : 0.0f;
-      q = fmaf(c, c, q);
-    }
-    const float rstd = rsqrtf(block_sum(q, red) / (float)D + 1e-6f);
+    float mean, rstd;
+    ln_row_stats(v, D, red, mean, rstd);
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
       const int d = threadIdx.x + 256 * j;
@@ -401,7 +243,7 @@ __global__ __launch_bounds__(256) void similarity_kernel(const float* __restrict
 
 hipError_t pool_logits(const void* x, int in_bf16, int64_t rows, int S, int D, const float* U, const bf16_t* Ut,
                        int H, float* logits, hipStream_t s) {
-  if (D % 64 || D > kPoolMaxD || H < 1 || H > kPwMaxH || rows % S) return hipErrorInvalidValue;
+  if (D % 64 || D > kPoolMaxD || H < 1 || H > kPoolMaxH || rows % S) return hipErrorInvalidValue;
   if (in_bf16 && Ut && S % 32 == 0) {
     const int64_t grid = (rows / 32 + 3) / 4;
     hipLaunchKernelGGL(pool_logits_mfma_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)x, rows, S,
@@ -409,24 +251,20 @@ hipError_t pool_logits(const void* x, int in_bf16, int64_t rows, int S, int D, c
     return hipGetLastError();
   }
   const int64_t grid = (rows + kPlRows - 1) / kPlRows;
-  const size_t lds = (size_t)H * D * 4;
-  if (D <= 1024) {
-    hipLaunchKernelGGL(pool_logits_kernel<16>, dim3((unsigned)grid), dim3(256), lds, s, x, in_bf16, rows, S, D, U, H,
-                       logits);
-    return hipGetLastError();
-  }
-  if (lds > 65536) {  // up to 16 x 1536 x 4 = 98,304 B of the CU's 160 KB
-    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&pool_logits_kernel<24>), kPwMaxH * kPoolMaxD * 4);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(pool_logits_kernel<24>, dim3((unsigned)grid), dim3(256), lds, s, x, in_bf16, rows, S, D, U, H,
-                     logits);
+  return launch_pool_scalar(&pool_logits_kernel<16>, &pool_logits_kernel<24>, dim3((unsigned)grid), D, H, s, x, in_bf16,
+                            rows, S, D, U, H, logits);
+}
+
+hipError_t pool_reduce(const float* part, int n, int64_t HD, int64_t groups, float* out, hipStream_t s) {
+  const int64_t total = groups * HD;
+  hipLaunchKernelGGL(pool_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, n, HD, total,
+                     out);
   return hipGetLastError();
 }
 
 hipError_t pool_softmax_wsum(const void* x, int in_bf16, int G, int S, int D, int H, const float* logits,
                              float* stats, float* zpart, float* z, hipStream_t s) {
-  if (D % 128 || D > kPoolMaxD || H < 1 || H > kPwMaxH) return hipErrorInvalidValue;
+  if (D % 128 || D > kPoolMaxD || H < 1 || H > kPoolMaxH) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pool_stats_kernel, dim3(G * H), dim3(256), 0, s, logits, S, stats);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
@@ -435,10 +273,7 @@ hipError_t pool_softmax_wsum(const void* x, int in_bf16, int G, int S, int D, in
                      C, zpart);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  const int64_t HD = (int64_t)H * D, total = (int64_t)G * HD;
-  hipLaunchKernelGGL(pool_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, zpart, C, HD, total,
-                     z);
-  return hipGetLastError();
+  return pool_reduce(zpart, C, (int64_t)H * D, G, z, s);
 }
 
 int pool_chunks(int S) { return (S + kPwRows - 1) / kPwRows; }

@@ -1,50 +1,29 @@
 // Training the classifier head (atten_pooler + projection, encoders.py:634-652) on frozen tokens: the
 // device-side fold of the forward and the kernels of the backward (vp_probe.cpp drives them).
 //
-// The forward pooler (clip_kernels.hip) folds the query into the key projection, U[h] = Wk[:,h,:] q~[h], and
-// streams the tokens twice (pool_logits, pool_wsum).  An engine folds on the host once; a head that is being
-// trained folds on the device every step:
+// The forward pooler folds the query into the key projection, U[h] = Wk[:,h,:] q~[h], and streams the tokens
+// twice (the two passes of pool_stream.h).  An engine folds on the host once; a head that is being trained folds
+// on the device every step:
 //   probe_fold_q  : q~[h][j] = qraw[h][j] * c * softplus(pds[j]),  qraw = query . Wq + bq, c = 1.442695041/sqrt(dh)
 //   probe_fold_u  : U[h][d] = Wk[d][h][:] . q~[h]; bf16 tokens: also Ut = (U_hi | U_lo | 0) as pool_split_u packs it,
 //                   and U itself becomes U_hi + U_lo, so the MFMA and the scalar logits kernels see one and the same key
 //   probe_pack    : Wv^T [H][D][dh], Wpost^T [H*dh][D] and gamma = 1 + scale, the layouts small_gemm / ln_l2_rows take
 // With the tokens frozen there is no dX, and the backward folds the same way.  With p = softmax_s(x . U[h]),
 // z = sum_s p x, enc = z Wv + bv and dz[b][h] = denc[b][h] Wv[:,h,:]^T:
-//   dp[b,h,s] = x[b,s] . dz[b,h]         pass 1 over the tokens: the shape of pool_logits with a per-clip "U"
+//   dp[b,h,s] = x[b,s] . dz[b,h]         pass 1 over the tokens, the operand per clip
 //   r[b,h]    = sum_s p dp = z[b,h] . dz[b,h]      (no pass: probe_dz_finish)
-//   dl        = p (dp - r)               written by pass 1 (probe_dl / probe_dl_mfma)
-//   dU[h]     = sum_{b,s} dl x[b,s]      pass 2: the shape of pool_wsum with signed weights (probe_wsum), chunk
+//   dl        = p (dp - r)               written by pass 1's store (probe_dl / probe_dl_mfma)
+//   dU[h]     = sum_{b,s} dl x[b,s]      pass 2 with dl as the signed weights (probe_wsum), chunk
 //                                        partials [B][C][H][D] summed over clips and chunks in index order
 //   dWk[:,h,:] = dU[h] (x) q~[h],  dq~[h] = Wk[:,h,:]^T dU[h],  dbk = 0 (the key bias cancels in the softmax)
 // Everything else is parameter-sized or [B][H][D]-sized: probe_gemm (strided, batched, the second operand's rows
 // contiguous in n: products and the "sum over b of outer products" of dWc, dWp, dWv), probe_dot (both operands
 // contiguous in k), probe_colsum (bias gradients), the LayerNorm and query backward kernels.  No atomics: every sum has one owner and a fixed order, so equal inputs give equal bits.
-#include "vp_common.h"
-#include "vp_kernels.h"
+#include "pool_stream.h"
 
 namespace vp {
 
 namespace {
-
-__device__ __forceinline__ float ldx(const void* p, int in_bf16, int64_t i) {
-  return in_bf16 ? bf2f(static_cast<const bf16_t*>(p)[i]) : static_cast<const float*>(p)[i];
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// block (256 threads) sum through LDS
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 __device__ __forceinline__ float softplus(float x) { return x > 20.0f ? x : log1pf(expf(x)); }
 
@@ -198,24 +177,15 @@ __global__ __launch_bounds__(256) void probe_ln_bwd_kernel(const float* __restri
   __shared__ float red[4];
   const int64_t r = blockIdx.x;
   float v[NV], g[NV];
-  float s = 0.0f;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
     const int d = threadIdx.x + 256 * j;
     const bool in = d < D;
     v[j] = in ? x[r * D + d] : 0.0f;
     g[j] = in ? dy[r * D + d] * gamma[d] : 0.0f;
-    s += v[j];
   }
-  const float mean = block_sum(s, red) / (float)D;
-  float q = 0.0f;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    const int d = threadIdx.x + 256 * j;
-    const float c = d < D ? v[j] - mean : 0.0f;
-    q = fmaf(c, c, q);
-  }
-  const float rstd = rsqrtf(block_sum(q, red) / (float)D + 1e-6f);
+  float mean, rstd;
+  ln_row_stats(v, D, red, mean, rstd);
   float sg = 0.0f, sgx = 0.0f;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
@@ -282,179 +252,50 @@ __global__ __launch_bounds__(256) void probe_dz_finish_kernel(const float* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// pass 1: dl[b][h][s] = p (x[b,s] . dz[b,h] - r[b,h]),  p = exp(logit - max) / sum as pool_wsum forms it
+// pass 1: dl[b][h][s] = p (x[b,s] . dz[b,h] - r[b,h]),  p = exp(logit - max) / sum as the forward forms it
 // ---------------------------------------------------------------------------------------------------------
-constexpr int kPlRows = 64;  // rows per workgroup (16 per wave)
-constexpr int kPwRows = 256;  // rows per chunk of pass 2 (pool_wsum's)
-constexpr int kPwMaxH = 16;
+struct StoreDl {
+  const float* __restrict__ logits;
+  const float* __restrict__ stats;
+  const float* __restrict__ r;
+  float* __restrict__ dl;
+  __device__ __forceinline__ void operator()(int64_t gh, int64_t idx, float dp) const {
+    dl[idx] = softmax_p(logits, stats, gh, idx) * (dp - r[gh]);
+  }
+};
 
-__device__ __forceinline__ float dl_value(const float* __restrict__ logits, const float* __restrict__ stats,
-                                          const float* __restrict__ r, int64_t gh, int64_t idx, float dp) {
-  const float p = __expf(logits[idx] - stats[2 * gh]) * stats[2 * gh + 1];
-  return p * (dp - r[gh]);
-}
-
-// dz of the workgroup's clip [H][D] in dynamic LDS (past 64 KB at 16 heads x 1408 columns: the launcher opts
-// in); grid (ceil(S / 64), B).  NJ: 64-column steps a lane keeps in registers, 16 (D <= 1024) or 24
+// pool_stream.h pass 1 with the operand of the workgroup's (wave's) clip: dz [B][H][D], dzt [B][32][D]
 template <int NJ>
 __global__ __launch_bounds__(256) void probe_dl_kernel(const void* __restrict__ x, int in_bf16, int S, int D,
                                                        const float* __restrict__ dz, int H,
                                                        const float* __restrict__ logits,
                                                        const float* __restrict__ stats, const float* __restrict__ r,
                                                        float* __restrict__ dl) {
-  extern __shared__ float dzs[];  // [H][D]
-  const int64_t b = blockIdx.y;
-  for (int i = threadIdx.x; i < H * D; i += 256) dzs[i] = dz[b * H * D + i];
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int nj = D >> 6;
-  for (int rr = 0; rr < kPlRows / 4; ++rr) {
-    const int s = blockIdx.x * kPlRows + w * (kPlRows / 4) + rr;
-    if (s >= S) break;  // uniform per wave
-    const int64_t row = b * S + s;
-    float xv[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) xv[j] = j < nj ? ldx(x, in_bf16, row * D + lane + 64 * j) : 0.0f;
-    float mine = 0.0f;  // lane h keeps head h's product
-    for (int h = 0; h < H; ++h) {
-      float a = 0.0f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-        if (j < nj) a = fmaf(xv[j], dzs[h * D + lane + 64 * j], a);
-      a = wave_sum(a);
-      if (lane == h) mine = a;
-    }
-    if (lane < H) {
-      const int64_t gh = b * H + lane, idx = gh * S + s;
-      dl[idx] = dl_value(logits, stats, r, gh, idx, mine);
-    }
-  }
+  pool_scalar_pass<NJ, true>(x, in_bf16, 0, S, D, dz, H, StoreDl{logits, stats, r, dl});
 }
 
-// bf16 tokens, S % 32 == 0: pool_logits_mfma_kernel's skinny GEMM on v_mfma_f32_32x32x16_bf16 with the B operand
-// of the wave's clip, dzt[g] [32][D] = (dz_hi | dz_lo | 0); lane c < H adds column H + c.  A wave's 32 rows lie in
-// one clip.
 __global__ __launch_bounds__(256) void probe_dl_mfma_kernel(const bf16_t* __restrict__ x, int64_t rows, int S, int D,
                                                             const bf16_t* __restrict__ dzt, int H,
                                                             const float* __restrict__ logits,
                                                             const float* __restrict__ stats,
                                                             const float* __restrict__ r, float* __restrict__ dl) {
-  const int lane = threadIdx.x & 63;
-  const int64_t r0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
-  if (r0 >= rows) return;  // whole wave
-  const int64_t g = r0 / S;
-  const int64_t s0 = r0 % S;
-  const int i = lane & 31, half = lane >> 5;
-  const bf16_t* ap = x + (r0 + i) * D + 8 * half;
-  const bf16_t* bp = dzt + (g * 32 + i) * D + 8 * half;
-  f32x16 acc = {};
-  const int nt = D >> 4;
-  int t = 0;
-  for (; t + 8 <= nt; t += 8) {
-    bf16x8 a[8], b[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      a[u] = *reinterpret_cast<const bf16x8*>(ap + 16 * (t + u));
-      b[u] = *reinterpret_cast<const bf16x8*>(bp + 16 * (t + u));
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u], b[u], acc, 0, 0, 0);
-  }
-  for (; t < nt; ++t) {
-    const bf16x8 a = *reinterpret_cast<const bf16x8*>(ap + 16 * t);
-    const bf16x8 b = *reinterpret_cast<const bf16x8*>(bp + 16 * t);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-  }
-  // acc[q] = C[row = (q&3) + 8(q>>2) + 4*half][col = i]
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const float v = acc[q] + __shfl_down(acc[q], H);
-    if (i < H) {
-      const int64_t gh = g * H + i, idx = gh * S + s0 + (q & 3) + 8 * (q >> 2) + 4 * half;
-      dl[idx] = dl_value(logits, stats, r, gh, idx, v);
-    }
-  }
+  pool_mfma_pass<true>(x, rows, S, D, dzt, H, StoreDl{logits, stats, r, dl});
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// pass 2: part[g][c][h][d] = sum over the rows of chunk c of dl[g,h,s] x[g*S+s][d]: pool_wsum_kernel's
-// decomposition (a workgroup owns one (g, 256-row chunk, 256-column block) with 128 threads, a thread two
-// adjacent columns and all 16 head sums of each, the chunk's weights in LDS, rows summed in row order; the
-// last column block of D = 128 odd is 128 wide and its second wave leaves after filling its share of the
-// weights), with the weights read as they are instead of formed from the logits
+// pass 2: part[g][c][h][d] = sum over the rows of chunk c of dl[g,h,s] x[g*S+s][d]: pool_stream.h pass 2 with the
+// signed weights read as they are, the [256][16] weights visited by head (consecutive threads read consecutive s)
 // ---------------------------------------------------------------------------------------------------------
+struct FillDl {
+  static constexpr bool kByRow = false;
+  const float* __restrict__ dl;
+  __device__ __forceinline__ float operator()(int64_t, int64_t idx) const { return dl[idx]; }
+};
+
 __global__ __launch_bounds__(128) void probe_wsum_kernel(const void* __restrict__ x, int in_bf16, int S, int D, int H,
                                                          const float* __restrict__ dl, int C,
                                                          float* __restrict__ part) {
-  __shared__ __attribute__((aligned(16))) float ws[kPwRows][kPwMaxH];
-  const int nq = (D + 255) >> 8;
-  const int q = blockIdx.x % nq;
-  const int gc = blockIdx.x / nq;
-  const int g = gc / C;
-  const int c = gc % C;
-  const int r0 = c * kPwRows;
-  const int nr = S - r0 < kPwRows ? S - r0 : kPwRows;
-  for (int i = threadIdx.x; i < kPwRows * kPwMaxH; i += 128) {
-    const int h = i / kPwRows, r = i % kPwRows;  // consecutive threads read consecutive s
-    ws[r][h] = (r < nr && h < H) ? dl[((int64_t)g * H + h) * S + r0 + r] : 0.0f;
-  }
-  __syncthreads();
-  const int d = q * 256 + 2 * threadIdx.x;
-  if (d >= D) return;  // the half block's second wave, whole
-  float acc0[kPwMaxH], acc1[kPwMaxH];
-#pragma unroll
-  for (int h = 0; h < kPwMaxH; ++h) acc0[h] = acc1[h] = 0.0f;
-  const int64_t rowbase = (int64_t)g * S + r0;
-  auto ld2 = [&](int r) -> float2 {
-    const int64_t i = (rowbase + r) * D + d;
-    if (in_bf16) {
-      const uint32_t u = *reinterpret_cast<const uint32_t*>(static_cast<const bf16_t*>(x) + i);
-      return make_float2(__uint_as_float(u << 16), __uint_as_float(u & 0xffff0000u));
-    }
-    return *reinterpret_cast<const float2*>(static_cast<const float*>(x) + i);
-  };
-  auto row = [&](int r, float2 xv) {
-    const float4* pr = reinterpret_cast<const float4*>(ws[r]);
-#pragma unroll
-    for (int h4 = 0; h4 < kPwMaxH / 4; ++h4) {
-      const float4 p = pr[h4];
-      acc0[4 * h4] = fmaf(p.x, xv.x, acc0[4 * h4]);
-      acc0[4 * h4 + 1] = fmaf(p.y, xv.x, acc0[4 * h4 + 1]);
-      acc0[4 * h4 + 2] = fmaf(p.z, xv.x, acc0[4 * h4 + 2]);
-      acc0[4 * h4 + 3] = fmaf(p.w, xv.x, acc0[4 * h4 + 3]);
-      acc1[4 * h4] = fmaf(p.x, xv.y, acc1[4 * h4]);
-      acc1[4 * h4 + 1] = fmaf(p.y, xv.y, acc1[4 * h4 + 1]);
-      acc1[4 * h4 + 2] = fmaf(p.z, xv.y, acc1[4 * h4 + 2]);
-      acc1[4 * h4 + 3] = fmaf(p.w, xv.y, acc1[4 * h4 + 3]);
-    }
-  };
-  int r = 0;
-  for (; r + 16 <= nr; r += 16) {
-    float2 xv[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) xv[u] = ld2(r + u);
-#pragma unroll
-    for (int u = 0; u < 16; ++u) row(r + u, xv[u]);
-  }
-  for (; r < nr; ++r) row(r, ld2(r));
-  float* zp = part + ((int64_t)g * C + c) * H * D + d;
-#pragma unroll
-  for (int h = 0; h < kPwMaxH; ++h)
-    if (h < H) *reinterpret_cast<float2*>(zp + (int64_t)h * D) = make_float2(acc0[h], acc1[h]);
-}
-
-// out[g][e] = sum_{i < n} part[g][i][e] in index order (chunks of a clip, then clips)
-__global__ __launch_bounds__(256) void probe_reduce_kernel(const float* __restrict__ part, int n, int64_t HD,
-                                                           int64_t total, float* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const int64_t g = i / HD, e = i % HD;
-  const float* p = part + g * n * HD + e;
-  float s = 0.0f;
-#pragma unroll 8
-  for (int c = 0; c < n; ++c) s += p[(int64_t)c * HD];
-  out[i] = s;
+  pool_wsum_pass(x, in_bf16, S, D, H, C, FillDl{dl}, part);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -550,7 +391,7 @@ hipError_t probe_ln_bwd(const float* x, const float* dy, const float* gamma, int
 
 hipError_t probe_dz_finish(const float* z, float* dz, int B, int H, int D, int split, bf16_t* dzt, float* r,
                            hipStream_t s) {
-  if (B < 1 || H < 1 || H > kPwMaxH || D < 1) return hipErrorInvalidValue;
+  if (B < 1 || H < 1 || H > kPoolMaxH || D < 1) return hipErrorInvalidValue;
   hipError_t e;
   if (split && (e = hipMemsetAsync(dzt, 0, (size_t)B * 32 * D * sizeof(bf16_t), s)) != hipSuccess) return e;
   hipLaunchKernelGGL(probe_dz_finish_kernel, dim3((B * H + 3) / 4), dim3(256), 0, s, z, dz, B * H, H, D, split, dzt, r);
@@ -561,7 +402,7 @@ bool probe_dl_uses_mfma(int in_bf16, int S) { return in_bf16 && S % 32 == 0; }
 
 hipError_t probe_dl(const void* x, int in_bf16, int B, int S, int D, int H, const float* dz, const bf16_t* dzt,
                     const float* logits, const float* stats, const float* r, float* dl, hipStream_t s) {
-  if (D % 64 || D > kPoolMaxD || H < 1 || H > kPwMaxH || B < 1 || S < 1 || B > 65535) return hipErrorInvalidValue;
+  if (D % 64 || D > kPoolMaxD || H < 1 || H > kPoolMaxH || B < 1 || S < 1 || B > 65535) return hipErrorInvalidValue;
   if (probe_dl_uses_mfma(in_bf16, S) && dzt) {
     const int64_t rows = (int64_t)B * S;
     const int64_t grid = (rows / 32 + 3) / 4;
@@ -569,23 +410,13 @@ hipError_t probe_dl(const void* x, int in_bf16, int B, int S, int D, int H, cons
                        H, logits, stats, r, dl);
     return hipGetLastError();
   }
-  const dim3 grid((S + kPlRows - 1) / kPlRows, B);
-  const size_t lds = (size_t)H * D * 4;
-  if (D <= 1024) {
-    hipLaunchKernelGGL(probe_dl_kernel<16>, grid, dim3(256), lds, s, x, in_bf16, S, D, dz, H, logits, stats, r, dl);
-    return hipGetLastError();
-  }
-  if (lds > 65536) {  // up to 16 x 1536 x 4 = 98,304 B of the CU's 160 KB
-    const hipError_t e = ensure_dyn_lds(reinterpret_cast<const void*>(&probe_dl_kernel<24>), kPwMaxH * kPoolMaxD * 4);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(probe_dl_kernel<24>, grid, dim3(256), lds, s, x, in_bf16, S, D, dz, H, logits, stats, r, dl);
-  return hipGetLastError();
+  return launch_pool_scalar(&probe_dl_kernel<16>, &probe_dl_kernel<24>, dim3((S + kPlRows - 1) / kPlRows, B), D, H, s, x,
+                            in_bf16, S, D, dz, H, logits, stats, r, dl);
 }
 
 hipError_t probe_wsum(const void* x, int in_bf16, int B, int S, int D, int H, const float* dl, float* part,
                       float* dUclip, float* dU, hipStream_t s) {
-  if (D % 128 || D > kPoolMaxD || H < 1 || H > kPwMaxH || B < 1 || S < 1) return hipErrorInvalidValue;
+  if (D % 128 || D > kPoolMaxD || H < 1 || H > kPoolMaxH || B < 1 || S < 1) return hipErrorInvalidValue;
   const int C = (S + kPwRows - 1) / kPwRows;
   hipLaunchKernelGGL(probe_wsum_kernel, dim3(B * C * ((D + 255) / 256)), dim3(128), 0, s, x, in_bf16, S, D, H, dl, C,
                      part);
@@ -593,11 +424,8 @@ hipError_t probe_wsum(const void* x, int in_bf16, int B, int S, int D, int H, co
   if (e != hipSuccess) return e;
   // over the chunks of each clip, then over the clips: B times the workgroups of one sweep over all B * C partials
   const int64_t HD = (int64_t)H * D;
-  hipLaunchKernelGGL(probe_reduce_kernel, dim3((unsigned)((B * HD + 255) / 256)), dim3(256), 0, s, part, C, HD, B * HD,
-                     dUclip);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(probe_reduce_kernel, dim3((unsigned)((HD + 255) / 256)), dim3(256), 0, s, dUclip, B, HD, HD, dU);
-  return hipGetLastError();
+  if ((e = pool_reduce(part, C, HD, B, dUclip, s)) != hipSuccess) return e;
+  return pool_reduce(dUclip, B, HD, 1, dU, s);
 }
 
 hipError_t probe_fold_bwd(const float* dU, const float* qt, int D, int H, float* dwk, hipStream_t s) {

@@ -13,31 +13,38 @@ using namespace vpi;
 
 namespace {
 constexpr int kMaxTextLen = 1024;  // L + 1 (CLS) tokens; TEXT_MAX_LEN is 64 (models.py:53)
-
-// what the pooler kernels take (clip_kernels.hip): whole 128-column blocks up to vp::kPoolMaxD, at most 16 heads
-int check_pooler_dims(const vp_config& v) {
-  if (v.num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
-  if (v.model_dim % 128 || v.model_dim > vp::kPoolMaxD)
-    return fail(VP_ENOTSUP, "pooler kernels need model_dim % 128 == 0, at most " + std::to_string(vp::kPoolMaxD));
-  return VP_OK;
-}
 }
 
-// AttenTokenPoolingLayer weights, packed (see pack_pooler): U [H][D] (query folded into the key
-// projection), Ut = bf16 hi|lo halves of U for the MFMA logits, Wv^T [H][D][dp], bv [H][dp],
-// Wpost^T [H*dp][D], bpost [D], LayerNorm gamma (1 + scale) / beta
-struct PoolerW {
-  void* Ut = nullptr;
-  float *U = nullptr, *WvT = nullptr, *bv = nullptr, *WpT = nullptr, *bp = nullptr;
-  float *ln_g = nullptr, *ln_b = nullptr;
-  int dp = 0;
-};
+namespace vpi {
+
+hipError_t pooler_stream(hipStream_t s, int bf, const PoolerW& pw, const void* feat, int G, int Sg, int D, int NH,
+                         const PoolScratch& sc) {
+  const hipError_t e = vp::pool_logits(feat, bf, (int64_t)G * Sg, Sg, D, pw.U, bf ? (const vp::bf16_t*)pw.Ut : nullptr,
+                                       NH, sc.logits, s);
+  if (e != hipSuccess) return e;
+  return vp::pool_softmax_wsum(feat, bf, G, Sg, D, NH, sc.logits, sc.stats, sc.zpart, sc.z, s);
+}
+
+hipError_t pooler_project(hipStream_t s, const PoolerW& pw, int G, int D, int NH, const PoolScratch& sc, int do_l2,
+                          float* dst) {
+  using namespace vp;
+  const int dp = pw.dp, K = NH * dp;
+  hipError_t e = small_gemm(sc.z, (int64_t)NH * D, D, pw.WvT, (int64_t)D * dp, pw.bv, dp, sc.enc, K, dp, G, dp, D, NH, s);
+  if (e != hipSuccess) return e;
+  const int splits = NH >= 8 && K % (8 * 128) == 0 && (size_t)8 * G * D <= sc.zpart_floats ? 8 : 1;
+  e = splits > 1 ? small_gemm_splitk(sc.enc, K, pw.WpT, pw.bp, sc.pooled, D, G, D, K, splits, sc.zpart, s)
+                 : small_gemm(sc.enc, K, 0, pw.WpT, 0, pw.bp, 0, sc.pooled, D, 0, G, D, K, 1, s);
+  if (e != hipSuccess) return e;
+  return ln_l2_rows(sc.pooled, 0, D, G, D, pw.ln_g, pw.ln_b, do_l2, dst, s);
+}
+
+}  // namespace vpi
 
 // What the two handles that wrap a FactorizedEncoder share: their own leaves (the ParamStore), the wrapped
 // handle and the prefix its leaves carry.  The wrapped encoder's leaves come first in the enumeration.
 struct WrapHandle : vpi::ParamStore {
   vp_handle* video = nullptr;
-  PoolerW pool;         // the AttenTokenPoolingLayer over the encoder's features
+  PoolerW pool;         // the AttenTokenPoolingLayer over the encoder's features, packed (pack_pooler)
   int64_t pool_dp = 0;  // its dim_per_head, set by *_create (pool.dp only once packed)
   bool bf16() const { return video->bf16(); }
   virtual ~WrapHandle() = default;
@@ -114,7 +121,8 @@ namespace {
 
 struct ClipVideoWs {
   size_t inner_bytes = 0;  // the wrapped encoder's own workspace, at `inner`
-  size_t inner = 0, feat = 0, logits = 0, stats = 0, zpart = 0, z = 0, enc = 0, pooled = 0, total = 0;
+  size_t inner = 0, feat = 0, total = 0;
+  PoolWs pool;
 };
 
 // vision features + pooler scratch for G <= B*T groups; dp = the pooler's dim_per_head
@@ -130,12 +138,7 @@ ClipVideoWs pool_video_ws(const vp_config& v, int64_t B, int64_t T, int64_t H, i
   size_t off = 0;
   L.inner = off; off = align256(off + inner_bytes);
   L.feat = off; off = align256(off + (size_t)Mp * D * es);
-  L.logits = off; off = align256(off + (size_t)M * NH * 4);
-  L.stats = off; off = align256(off + (size_t)B * T * NH * 8);
-  L.zpart = off; off = align256(off + (size_t)gc * NH * D * 4);
-  L.z = off; off = align256(off + (size_t)B * T * NH * D * 4);
-  L.enc = off; off = align256(off + (size_t)B * T * NH * dp * 4);
-  L.pooled = off; off = align256(off + (size_t)B * T * D * 4);
+  L.pool = carve_pool_ws(off, M, B * T, D, NH, dp, (size_t)gc * NH * D);
   L.total = off;
   return L;
 }
@@ -259,41 +262,31 @@ int pack_pooler(ParamStore& c, const std::string& root, int64_t D, int64_t H, in
   std::vector<uint16_t> ut((size_t)32 * D);
   pool_split_u(U.data(), H, D, ut.data());
   int rc;
-  if ((rc = c.upload(ut.data(), ut.size() * 2, &pw.Ut))) return rc;
-  if ((rc = c.upload_f32(U, &pw.U)) || (rc = c.upload_f32(wvt, &pw.WvT)) || (rc = c.upload_f32(bv, &pw.bv)) ||
-      (rc = c.upload_f32(wpt, &pw.WpT)) || (rc = c.upload_f32(bp, &pw.bp)) || (rc = c.upload_f32(g, &pw.ln_g)) ||
-      (rc = c.upload_f32(c.data(root + "pooling_attention_layer_norm/bias"), &pw.ln_b)))
+  void* utd = nullptr;
+  if ((rc = c.upload(ut.data(), ut.size() * 2, &utd))) return rc;
+  pw.Ut = utd;
+  auto up = [&](const std::vector<float>& v, const float** out) {
+    float* p = nullptr;
+    const int r = c.upload_f32(v, &p);
+    *out = p;
+    return r;
+  };
+  if ((rc = up(U, &pw.U)) || (rc = up(wvt, &pw.WvT)) || (rc = up(bv, &pw.bv)) || (rc = up(wpt, &pw.WpT)) ||
+      (rc = up(bp, &pw.bp)) || (rc = up(g, &pw.ln_g)) ||
+      (rc = up(c.data(root + "pooling_attention_layer_norm/bias"), &pw.ln_b)))
     return rc;
   return VP_OK;
 }
 
 // pooler over G groups of Sg rows of feat [G*Sg][D] -> dst [G][D] fp32 (LayerNorm, then L2 if do_l2)
-struct PoolScratch {
-  float *logits, *stats, *zpart, *z, *enc, *pooled;
-  size_t zpart_floats;  // capacity of zpart (the output projection's split-K partials reuse it)
-};
-
 int run_pooler(Fwd& f, const PoolerW& pw, const void* feat, int M, int G, int Sg, int D, int NH,
                const PoolScratch& sc, int do_l2, float* dst) {
-  using namespace vp;
   const int dp = pw.dp;
   const double bytes = 2.0 * M * D * (f.bf ? 2 : 4);  // two streaming passes over the tokens
-  VP_HIP(f.rec(PC_POOL, 2.0 * 2.0 * M * D * NH, bytes, [&] {
-    hipError_t e = pool_logits(feat, f.bf, M, Sg, D, pw.U, (const bf16_t*)pw.Ut, NH, sc.logits, f.s);
-    if (e != hipSuccess) return e;
-    return pool_softmax_wsum(feat, f.bf, G, Sg, D, NH, sc.logits, sc.stats, sc.zpart, sc.z, f.s); }));
-  // the value projection per head, then the output projection over K = NH * dp split 8 ways into zpart (free
-  // again once z is summed; sized for >= G * NH * D floats), then LayerNorm (+ L2)
-  const int splits = NH >= 8 && (NH * dp) % (8 * 128) == 0 && (size_t)8 * G * D <= sc.zpart_floats ? 8 : 1;
-  VP_HIP(f.rec(PC_POOL, 2.0 * G * D * (double)dp * NH * 2.0, 4.0 * (double)NH * D * dp * 2.0, [&] {
-    hipError_t e = small_gemm(sc.z, (int64_t)NH * D, D, pw.WvT, (int64_t)D * dp, pw.bv, dp, sc.enc, (int64_t)NH * dp,
-                              dp, G, dp, D, NH, f.s);
-    if (e != hipSuccess) return e;
-    e = splits > 1 ? small_gemm_splitk(sc.enc, (int64_t)NH * dp, pw.WpT, pw.bp, sc.pooled, D, G, D, NH * dp, splits,
-                                       sc.zpart, f.s)
-                   : small_gemm(sc.enc, (int64_t)NH * dp, 0, pw.WpT, 0, pw.bp, 0, sc.pooled, D, 0, G, D, NH * dp, 1, f.s);
-    if (e != hipSuccess) return e;
-    return ln_l2_rows(sc.pooled, 0, D, G, D, pw.ln_g, pw.ln_b, do_l2, dst, f.s); }));
+  VP_HIP(f.rec(PC_POOL, 2.0 * 2.0 * M * D * NH, bytes,
+               [&] { return pooler_stream(f.s, f.bf, pw, feat, G, Sg, D, NH, sc); }));
+  VP_HIP(f.rec(PC_POOL, 2.0 * G * D * (double)dp * NH * 2.0, 4.0 * (double)NH * D * dp * 2.0,
+               [&] { return pooler_project(f.s, pw, G, D, NH, sc, do_l2, dst); }));
   return VP_OK;
 }
 
@@ -346,9 +339,7 @@ int vision_features(WrapHandle* w, const VideoSrc& src, int64_t B, int64_t T, in
   if (spatiotemporal_out)
     VP_HIP(hipMemcpyAsync(spatiotemporal_out, vf->feat, (size_t)M64 * v.model_dim * dtype_bytes(v.fprop_dtype),
                           hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  vf->sc = PoolScratch{f32(L.logits), f32(L.stats), f32(L.zpart), f32(L.z), f32(L.enc), f32(L.pooled),
-                       (L.z - L.zpart) / 4};
+  vf->sc = L.pool.at(ws);
   return VP_OK;
 }
 
@@ -387,12 +378,13 @@ int vp_clip_create(const vp_clip_config* cfg, int device, vp_clip** out) {
   *out = nullptr;
   if (cfg->num_auxiliary_layers < 0 || cfg->num_unimodal_layers < 0 || cfg->vocabulary_size < 1)
     return fail(VP_EINVAL, "bad LvT configuration");
-  if (cfg->video.num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
+  if (int rc = check_pooler_heads(cfg->video.num_heads)) return rc;
   if (cfg->norm_policy != 0 && cfg->norm_policy != 1)
     return fail(VP_ENOTSUP, "norm_policy must be 0 ('pre') or 1 ('primer_hybrid', the text tower's)");
   vp_clip* c = new vp_clip();
   int rc = c->init(&cfg->video, device, "vision_encoder/");
-  if (!rc) rc = check_pooler_dims(cfg->video);  // after the encoder's own refusals (dim_per_head, bf16 widths)
+  // after the encoder's own refusals (dim_per_head, bf16 widths)
+  if (!rc) rc = check_pooler_dims(cfg->video.model_dim, cfg->video.num_heads);
   if (rc) {
     wrap_destroy(c);
     return rc;
@@ -607,10 +599,10 @@ int vp_classifier_create(const vp_config* cfg, int num_classes, int device, vp_c
   if (!cfg || !out) return fail(VP_EINVAL, "null argument");
   *out = nullptr;
   if (num_classes < 1) return fail(VP_EINVAL, "num_classes must be positive");
-  if (cfg->num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
+  if (int rc = check_pooler_heads(cfg->num_heads)) return rc;
   vp_classifier* c = new vp_classifier();
   int rc = c->init(cfg, device, "encoder/");
-  if (!rc) rc = check_pooler_dims(*cfg);
+  if (!rc) rc = check_pooler_dims(cfg->model_dim, cfg->num_heads);
   if (rc) {
     wrap_destroy(c);
     return rc;
@@ -754,25 +746,6 @@ namespace {
 
 bool float_dtype(int dtype) { return dtype == VP_F32 || dtype == VP_BF16; }
 
-// scratch of one run_pooler call over G groups of S rows: PoolScratch's fields in order, zpart holding the
-// G * pool_chunks(S) chunk sums (as pool_video_ws sizes it for its larger grouping)
-struct DevPoolWs {
-  size_t logits = 0, stats = 0, zpart = 0, z = 0, enc = 0, pooled = 0, total = 0;
-};
-
-DevPoolWs dev_pool_ws(int64_t G, int64_t S, int64_t D, int64_t NH, int64_t dp) {
-  DevPoolWs L;
-  size_t off = 0;
-  L.logits = off; off = align256(off + (size_t)G * S * NH * 4);
-  L.stats = off; off = align256(off + (size_t)G * NH * 8);
-  L.zpart = off; off = align256(off + (size_t)G * vp::pool_chunks((int)S) * NH * D * 4);
-  L.z = off; off = align256(off + (size_t)G * NH * D * 4);
-  L.enc = off; off = align256(off + (size_t)G * NH * dp * 4);
-  L.pooled = off; off = align256(off + (size_t)G * D * 4);
-  L.total = off;
-  return L;
-}
-
 }  // namespace
 
 extern "C" {
@@ -780,7 +753,8 @@ extern "C" {
 // Host only, no GPU call: the production packing of U [H][D] fp32 into ut [32][D] bf16 bits (pool_split_u).
 int vp_dev_pool_split_u(const float* U_host, int64_t H, int64_t D, uint16_t* ut_host) {
   if (!U_host || !ut_host) return fail(VP_EINVAL, "null argument");
-  if (H < 1 || H > 16 || D < 1) return fail(VP_EINVAL, "pool_split_u: 1 <= H <= 16 and D >= 1");
+  if (H < 1 || H > vp::kPoolMaxH || D < 1)
+    return fail(VP_EINVAL, "pool_split_u: 1 <= H <= " + std::to_string(vp::kPoolMaxH) + " and D >= 1");
   pool_split_u(U_host, H, D, ut_host);
   return VP_OK;
 }
@@ -796,7 +770,7 @@ static int dev_pool_logits(const void* x, int in_dtype, int64_t rows, int64_t S,
   if (rows < 1 || S < 1 || rows % S) return fail(VP_EINVAL, "pool_logits: rows must be a positive multiple of S");
   if (D < 64 || D % 64 || D > max_d)
     return fail(VP_EINVAL, "pool_logits: D must be a multiple of 64, at most " + std::to_string(max_d));
-  if (H < 1 || H > 16) return fail(VP_EINVAL, "pool_logits: 1 <= H <= 16");
+  if (H < 1 || H > vp::kPoolMaxH) return fail(VP_EINVAL, "pool_logits: 1 <= H <= " + std::to_string(vp::kPoolMaxH));
   if (rows / 64 + 1 > 0x7fffffff) return fail(VP_EINVAL, "pool_logits: too many rows");
   VP_HIP(vp::pool_logits(x, in_dtype == VP_BF16, rows, (int)S, (int)D, U, (const vp::bf16_t*)Ut, (int)H, logits,
                          static_cast<hipStream_t>(stream)));
@@ -822,7 +796,8 @@ static int dev_pool_softmax_wsum(const void* x, int in_dtype, int64_t G, int64_t
   if (D < block || D % block || D > max_d)
     return fail(VP_EINVAL, "pool_softmax_wsum: D must be a multiple of " + std::to_string(block) + ", at most " +
                                std::to_string(max_d));
-  if (H < 1 || H > 16) return fail(VP_EINVAL, "pool_softmax_wsum: 1 <= H <= 16");
+  if (H < 1 || H > vp::kPoolMaxH)
+    return fail(VP_EINVAL, "pool_softmax_wsum: 1 <= H <= " + std::to_string(vp::kPoolMaxH));
   VP_HIP(vp::pool_softmax_wsum(x, in_dtype == VP_BF16, (int)G, (int)S, (int)D, (int)H, logits, stats, zpart, z,
                                static_cast<hipStream_t>(stream)));
   return VP_OK;
@@ -925,22 +900,20 @@ int vp_dev_pooler(int kind, void* handle, const void* feat, int64_t G, int64_t S
   if (G < 1 || S < 1 || G * S > 0x7fffffff) return fail(VP_EINVAL, "pooler: bad G or S");
   const vp_config& v = w->video->cfg;
   const int D = v.model_dim, NH = v.num_heads;
-  if (int rc = check_pooler_dims(v)) return rc;
-  const DevPoolWs L = dev_pool_ws(G, S, D, NH, w->pool.dp);
+  if (int rc = check_pooler_dims(D, NH)) return rc;
+  // zpart holds the G * pool_chunks(S) chunk sums (as pool_video_ws sizes it for its larger grouping)
+  size_t total = 0;
+  const PoolWs L = carve_pool_ws(total, G * S, G, D, NH, w->pool.dp, (size_t)G * vp::pool_chunks((int)S) * NH * D);
   if (!scratch) {
-    *scratch_bytes = L.total;
+    *scratch_bytes = total;
     return VP_OK;
   }
   if (!feat || !dst) return fail(VP_EINVAL, "null argument");
-  if (*scratch_bytes < L.total) return fail(VP_EINVAL, "scratch too small: need " + std::to_string(L.total));
+  if (*scratch_bytes < total) return fail(VP_EINVAL, "scratch too small: need " + std::to_string(total));
   VP_HIP(hipSetDevice(w->device));
-  char* ws = static_cast<char*>(scratch);
-  auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  const PoolScratch sc{f32(L.logits), f32(L.stats), f32(L.zpart), f32(L.z), f32(L.enc), f32(L.pooled),
-                       (L.z - L.zpart) / 4};
   Fwd f;
   f.s = static_cast<hipStream_t>(stream); f.bf = w->bf16(); f.M = (int)(G * S); f.D = D; f.NH = NH;
-  return run_pooler(f, w->pool, feat, (int)(G * S), (int)G, (int)S, D, NH, sc, do_l2, dst);
+  return run_pooler(f, w->pool, feat, (int)(G * S), (int)G, (int)S, D, NH, L.at(scratch), do_l2, dst);
 }
 
 }  // extern "C"

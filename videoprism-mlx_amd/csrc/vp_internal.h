@@ -330,6 +330,66 @@ struct WsLayout {
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// ---- the attention pooler's forward (AttenTokenPoolingLayer; pool_stream.h, clip_kernels.hip), as the video-text
+// and classifier engines run it on packed weights and as the head's training op runs it on weights it folds ----
+// what the pooler kernels take: whole 128-column blocks up to vp::kPoolMaxD, at most vp::kPoolMaxH heads
+inline int check_pooler_heads(int64_t num_heads) {
+  if (num_heads > vp::kPoolMaxH)
+    return fail(VP_ENOTSUP, "pooler kernels support up to " + std::to_string(vp::kPoolMaxH) + " heads");
+  return VP_OK;
+}
+inline int check_pooler_dims(int64_t model_dim, int64_t num_heads) {
+  if (int rc = check_pooler_heads(num_heads)) return rc;
+  if (model_dim % 128 || model_dim > vp::kPoolMaxD)
+    return fail(VP_ENOTSUP, "pooler kernels need model_dim % 128 == 0, at most " + std::to_string(vp::kPoolMaxD));
+  return VP_OK;
+}
+
+// The weights in the layouts the kernels take (device pointers): U [H][D] (query folded into the key projection),
+// Ut = bf16 hi|lo halves of U for the MFMA logits, Wv^T [H][D][dp], bv [H][dp], Wpost^T [H*dp][D], bpost [D],
+// LayerNorm gamma (1 + scale) / beta
+struct PoolerW {
+  const void* Ut = nullptr;
+  const float *U = nullptr, *WvT = nullptr, *bv = nullptr, *WpT = nullptr, *bp = nullptr;
+  const float *ln_g = nullptr, *ln_b = nullptr;
+  int dp = 0;
+};
+
+// scratch of one forward over G groups: logits [rows][H], stats [G][H][2], zpart (the chunk sums; the output
+// projection's split-K partials reuse it), z [G][H][D], enc [G][H*dp], pooled [G][D]
+struct PoolScratch {
+  float *logits, *stats, *zpart, *z, *enc, *pooled;
+  size_t zpart_floats;  // capacity of zpart
+};
+
+// its byte offsets in a workspace, carved from `off` on in that order
+struct PoolWs {
+  size_t logits = 0, stats = 0, zpart = 0, z = 0, enc = 0, pooled = 0;
+  PoolScratch at(void* base) const {
+    auto f32 = [&](size_t o) { return reinterpret_cast<float*>(static_cast<char*>(base) + o); };
+    return PoolScratch{f32(logits), f32(stats), f32(zpart), f32(z), f32(enc), f32(pooled), (z - zpart) / 4};
+  }
+};
+inline PoolWs carve_pool_ws(size_t& off, int64_t rows, int64_t G, int64_t D, int64_t NH, int64_t dp,
+                            size_t zpart_floats) {
+  PoolWs L;
+  L.logits = off; off = align256(off + (size_t)rows * NH * 4);
+  L.stats = off; off = align256(off + (size_t)G * NH * 8);
+  L.zpart = off; off = align256(off + zpart_floats * 4);
+  L.z = off; off = align256(off + (size_t)G * NH * D * 4);
+  L.enc = off; off = align256(off + (size_t)G * NH * dp * 4);
+  L.pooled = off; off = align256(off + (size_t)G * D * 4);
+  return L;
+}
+
+// The two streaming passes over feat [G*Sg][D] (bf: bf16, else fp32): logits, softmax statistics, z (vp_clip.cpp)
+hipError_t pooler_stream(hipStream_t s, int bf, const PoolerW& pw, const void* feat, int G, int Sg, int D, int NH,
+                         const PoolScratch& sc);
+// ... then the value projection per head, the output projection over K = NH * dp (split 8 ways into zpart, free
+// again once z is summed, where that fills the device), LayerNorm and, if do_l2, L2 -> dst [G][D]
+hipError_t pooler_project(hipStream_t s, const PoolerW& pw, int G, int D, int NH, const PoolScratch& sc, int do_l2,
+                          float* dst);
+
 // GEMM row count: B*T*N padded to the GEMM tile (256 rows bf16, 128 fp32); the padding rows
 // ride through the row-independent GEMM / LayerNorm kernels and are never read back
 inline int64_t padded_rows(const vp_handle* h, int64_t M) {

@@ -204,6 +204,7 @@ hipError_t attention_masked(const void* qkv, void* o, int in_is_bf16, int num_se
                             float cap, const float* key_pad, int causal, hipStream_t s, int dh = 64);
 // widest rows the pooler kernels take (pool_logits: D = 64 k; pool_softmax_wsum: D = 128 k; ln_l2_rows: any D)
 constexpr int kPoolMaxD = 1536;
+constexpr int kPoolMaxH = 16;  // most heads they take (a thread of the weighted sum keeps every head's sums)
 // contrastive pooler: logits[g][h][s] = x[g*S+s] . U[h]; then softmax per (g,h) and
 // z[g][h][:] = sum_s p x (zpart scratch: [G][pool_chunks(S)][H][D], stats [G*H][2])
 // (bf16 x with Ut = [32][D] bf16 (U_hi | U_lo | 0) and S % 32 == 0: MFMA kernel)
@@ -212,6 +213,8 @@ hipError_t pool_logits(const void* x, int in_bf16, int64_t rows, int S, int D, c
 hipError_t pool_softmax_wsum(const void* x, int in_bf16, int G, int S, int D, int H, const float* logits,
                              float* stats, float* zpart, float* z, hipStream_t s);
 int pool_chunks(int S);
+// out[g][e] = sum_{i < n} part[g][i][e] in index order, e < HD, g < groups (chunk sums of a weighted-sum pass)
+hipError_t pool_reduce(const float* part, int n, int64_t HD, int64_t groups, float* out, hipStream_t s);
 // out[b][m][n] = A[b][m][:] . Wt[b][:][n] + bias[b][n] (fp32, small M), batch strides sA/sW/sB/sO
 hipError_t small_gemm(const float* A, int64_t lda, int64_t sA, const float* Wt, int64_t sW, const float* bias,
                       int64_t sB, float* out, int64_t ldo, int64_t sO, int M, int N, int K, int batch,

@@ -1,19 +1,21 @@
 // C-ABI of the classifier head's training ops (vp_op_probe_*): forward and backward of atten_pooler + projection
 // (encoders.py:634-652) over frozen tokens.  The forward folds the query into the key projection on the device
-// (probe_kernels.hip) and then runs the launches of run_pooler (vp_clip.cpp) and the projection; the backward is
-// steps 1-8 of probe_kernels.hip's header, two streaming passes over the tokens and parameter-sized products.
+// (probe_kernels.hip) and then runs the engines' pooler forward (pooler_stream, pooler_project) and the projection;
+// the backward is steps 1-8 below, two streaming passes over the tokens and parameter-sized products.
 #include "vp_internal.h"
 
 using namespace vpi;
 
 namespace {
 
-// forward state the backward reads, then the backward's own scratch (offsets in bytes)
+// forward state the backward reads (the folded weights, the pooler's scratch, emb), then the backward's own
+// scratch (offsets in bytes)
 struct ProbeWs {
   size_t qraw = 0, qt = 0, U = 0, Ut = 0, wvt = 0, wpt = 0, gamma = 0;
-  size_t logits = 0, stats = 0, zpart = 0, z = 0, enc = 0, pooled = 0, emb = 0;
+  PoolWs fw;
+  size_t emb = 0;
   size_t demb = 0, dpooled = 0, lnst = 0, denc = 0, dz = 0, dzt = 0, r = 0, dl = 0, dUclip = 0, dU = 0, dqt = 0;
-  size_t zpart_floats = 0, total = 0;
+  size_t total = 0;
 };
 
 ProbeWs probe_ws(int64_t D, int64_t H, int64_t B, int64_t S) {
@@ -32,14 +34,9 @@ ProbeWs probe_ws(int64_t D, int64_t H, int64_t B, int64_t S) {
   L.wvt = take((size_t)D * D * f);
   L.wpt = take((size_t)D * D * f);
   L.gamma = take(D * f);
-  L.logits = take((size_t)B * H * S * f);
-  L.stats = take((size_t)B * H * 2 * f);
-  // chunk sums of both weighted-sum passes; the output projection's 8 split-K partials reuse it
-  L.zpart_floats = std::max<size_t>((size_t)B * vp::pool_chunks((int)S) * H * D, (size_t)8 * B * D);
-  L.zpart = take(L.zpart_floats * f);
-  L.z = take((size_t)B * H * D * f);
-  L.enc = take((size_t)B * D * f);
-  L.pooled = take((size_t)B * D * f);
+  // zpart: chunk sums of both weighted-sum passes; the output projection's 8 split-K partials reuse it
+  L.fw = carve_pool_ws(off, B * S, B, D, H, D / H,
+                       std::max<size_t>((size_t)B * vp::pool_chunks((int)S) * H * D, (size_t)8 * B * D));
   L.emb = take((size_t)B * D * f);
   L.demb = take((size_t)B * D * f);
   L.dpooled = take((size_t)B * D * f);
@@ -61,24 +58,17 @@ int check_probe_shape(const vp_probe_dims* dims, int64_t B, int64_t S) {
   if (B < 1 || S < 1) return fail(VP_EINVAL, "probe: tokens must be [B, S, D] with B >= 1 and S >= 1");
   if (dims->model_dim < 1 || dims->num_heads < 1 || dims->num_classes < 1)
     return fail(VP_EINVAL, "probe: model_dim, num_heads and num_classes must be positive");
-  // what the pooler kernels take (clip_kernels.hip; vp_clip.cpp check_pooler_dims)
-  if (dims->num_heads > 16) return fail(VP_ENOTSUP, "pooler kernels support up to 16 heads");
-  if (dims->model_dim % 128 || dims->model_dim > vp::kPoolMaxD)
-    return fail(VP_ENOTSUP, "pooler kernels need model_dim % 128 == 0, at most " + std::to_string(vp::kPoolMaxD));
+  if (int rc = check_pooler_dims(dims->model_dim, dims->num_heads)) return rc;
   if (dims->model_dim % dims->num_heads)
     return fail(VP_ENOTSUP, "probe: model_dim must be a multiple of num_heads");
   if (B > 65535 || B * S > 0x7fffffff) return fail(VP_ENOTSUP, "probe: at most 65535 clips and 2^31 - 1 tokens");
   return VP_OK;
 }
 
-bool any_null(const vp_probe_params& p) {
+template <class Leaves>  // vp_probe_params or vp_probe_grads: the same 14 names
+bool any_null(const Leaves& p) {
   return !p.query || !p.per_dim_scale || !p.query_w || !p.query_b || !p.key_w || !p.key_b || !p.value_w ||
          !p.value_b || !p.post_w || !p.post_b || !p.ln_scale || !p.ln_bias || !p.proj_kernel || !p.proj_bias;
-}
-
-bool any_null(const vp_probe_grads& g) {
-  return !g.query || !g.per_dim_scale || !g.query_w || !g.query_b || !g.key_w || !g.key_b || !g.value_w ||
-         !g.value_b || !g.post_w || !g.post_b || !g.ln_scale || !g.ln_bias || !g.proj_kernel || !g.proj_bias;
 }
 
 int check_probe_call(const vp_probe_dims* dims, int dtype, int64_t B, int64_t S, size_t ws_bytes, ProbeWs* L) {
@@ -117,16 +107,11 @@ int vp_op_probe_forward(const vp_probe_dims* dims, const vp_probe_params* params
   VP_HIP(probe_gemm(p.query, 0, 0, 1, p.query_w, 0, D, f32(L.qraw), 0, D, 1, D, D, 1, s));
   VP_HIP(probe_fold(f32(L.qraw), p.query_b, p.per_dim_scale, p.key_w, D, H, bf, f32(L.qt), f32(L.U), Ut, s));
   VP_HIP(probe_pack(p.value_w, p.post_w, p.ln_scale, D, H, f32(L.wvt), f32(L.wpt), f32(L.gamma), s));
-  // run_pooler's launches: two streaming passes, the value projection per head, the output projection, LayerNorm
-  VP_HIP(pool_logits(tokens, bf, B * S, (int)S, D, f32(L.U), bf ? Ut : nullptr, H, f32(L.logits), s));
-  VP_HIP(pool_softmax_wsum(tokens, bf, G, (int)S, D, H, f32(L.logits), f32(L.stats), f32(L.zpart), f32(L.z), s));
-  VP_HIP(small_gemm(f32(L.z), (int64_t)H * D, D, f32(L.wvt), (int64_t)D * dh, p.value_b, dh, f32(L.enc), D, dh, G, dh,
-                    D, H, s));
-  if (H >= 8 && D % (8 * 128) == 0)
-    VP_HIP(small_gemm_splitk(f32(L.enc), D, f32(L.wpt), p.post_b, f32(L.pooled), D, G, D, D, 8, f32(L.zpart), s));
-  else
-    VP_HIP(small_gemm(f32(L.enc), D, 0, f32(L.wpt), 0, p.post_b, 0, f32(L.pooled), D, 0, G, D, D, 1, s));
-  VP_HIP(ln_l2_rows(f32(L.pooled), 0, D, G, D, f32(L.gamma), p.ln_bias, 0, f32(L.emb), s));
+  // the pooler's forward on the folded weights, then the projection
+  const PoolerW pw{Ut, f32(L.U), f32(L.wvt), p.value_b, f32(L.wpt), p.post_b, f32(L.gamma), p.ln_bias, dh};
+  const PoolScratch sc = L.fw.at(ws);
+  VP_HIP(pooler_stream(s, bf, pw, tokens, G, (int)S, D, H, sc));
+  VP_HIP(pooler_project(s, pw, G, D, H, sc, 0, f32(L.emb)));
   VP_HIP(small_gemm(f32(L.emb), D, 0, p.proj_kernel, 0, p.proj_bias, 0, logits, C, 0, G, C, D, 1, s));
   if (emb) VP_HIP(hipMemcpyAsync(emb, f32(L.emb), (size_t)B * D * 4, hipMemcpyDeviceToDevice, s));
   return VP_OK;
@@ -154,23 +139,23 @@ int vp_op_probe_backward(const vp_probe_dims* dims, const vp_probe_params* param
   VP_HIP(probe_gemm(f32(L.emb), 0, 1, D, dlogits, 0, C, g.proj_kernel, 0, C, D, C, G, 1, s));
   VP_HIP(probe_colsum(dlogits, G, C, g.proj_bias, s));
   // 2. LayerNorm
-  VP_HIP(probe_ln_bwd(f32(L.pooled), f32(L.demb), f32(L.gamma), G, D, f32(L.dpooled), f32(L.lnst), g.ln_scale,
+  VP_HIP(probe_ln_bwd(f32(L.fw.pooled), f32(L.demb), f32(L.gamma), G, D, f32(L.dpooled), f32(L.lnst), g.ln_scale,
                       g.ln_bias, s));
   // 3. post projection: dWp[d][h][j] = sum_b dpooled[b][d] enc[b][h][j], denc = dpooled Wp (small_gemm takes this
   // layout too, but its 12 workgroups run the K = D loop in 55 us at B = 32 where the 16-way K split takes a fifth)
-  VP_HIP(probe_gemm(f32(L.dpooled), 0, 1, D, f32(L.enc), 0, D, g.post_w, 0, D, D, D, G, 1, s));
+  VP_HIP(probe_gemm(f32(L.dpooled), 0, 1, D, f32(L.fw.enc), 0, D, g.post_w, 0, D, D, D, G, 1, s));
   VP_HIP(probe_colsum(f32(L.dpooled), G, D, g.post_b, s));
   VP_HIP(probe_gemm(f32(L.dpooled), 0, D, 1, p.post_w, 0, D, f32(L.denc), 0, D, G, D, D, 1, s));
   // 4. value projection, per head: dWv[:,h,:] = sum_b z[b,h]^T denc[b,h], dz[b,h] = denc[b,h] Wv[:,h,:]^T
-  VP_HIP(probe_gemm(f32(L.z), D, 1, HD, f32(L.denc), dh, D, g.value_w, dh, D, D, dh, G, H, s));
+  VP_HIP(probe_gemm(f32(L.fw.z), D, 1, HD, f32(L.denc), dh, D, g.value_w, dh, D, D, dh, G, H, s));
   VP_HIP(probe_colsum(f32(L.denc), G, D, g.value_b, s));
   VP_HIP(probe_dot(f32(L.denc), dh, D, p.value_w, dh, D, f32(L.dz), D, HD, G, D, dh, H, s));
   // 5. r = z . dz (the softmax term needs no pass) and, for bf16 tokens, the hi | lo operand of each clip; pass 1
-  VP_HIP(probe_dz_finish(f32(L.z), f32(L.dz), G, H, D, bf, dzt, f32(L.r), s));
-  VP_HIP(probe_dl(tokens, bf, G, (int)S, D, H, f32(L.dz), bf ? dzt : nullptr, f32(L.logits), f32(L.stats), f32(L.r),
+  VP_HIP(probe_dz_finish(f32(L.fw.z), f32(L.dz), G, H, D, bf, dzt, f32(L.r), s));
+  VP_HIP(probe_dl(tokens, bf, G, (int)S, D, H, f32(L.dz), bf ? dzt : nullptr, f32(L.fw.logits), f32(L.fw.stats), f32(L.r),
                   f32(L.dl), s));
   // 6. pass 2
-  VP_HIP(probe_wsum(tokens, bf, G, (int)S, D, H, f32(L.dl), f32(L.zpart), f32(L.dUclip), f32(L.dU), s));
+  VP_HIP(probe_wsum(tokens, bf, G, (int)S, D, H, f32(L.dl), f32(L.fw.zpart), f32(L.dUclip), f32(L.dU), s));
   // 7. fold: dWk = dU (x) q~, dq~[h] = Wk[:,h,:]^T dU[h], dbk = 0
   VP_HIP(probe_fold_bwd(f32(L.dU), f32(L.qt), D, H, g.key_w, s));
   VP_HIP(hipMemsetAsync(g.key_b, 0, (size_t)D * 4, s));
@@ -199,9 +184,9 @@ int vp_dev_probe_backward_pass(const vp_probe_dims* dims, const void* tokens, in
   auto f32 = [&](size_t off) { return reinterpret_cast<float*>(w + off); };
   if (which == 1)
     VP_HIP(probe_dl(tokens, bf, (int)B, (int)S, D, H, f32(L.dz), bf ? reinterpret_cast<bf16_t*>(w + L.dzt) : nullptr,
-                    f32(L.logits), f32(L.stats), f32(L.r), f32(L.dl), s));
+                    f32(L.fw.logits), f32(L.fw.stats), f32(L.r), f32(L.dl), s));
   else
-    VP_HIP(probe_wsum(tokens, bf, (int)B, (int)S, D, H, f32(L.dl), f32(L.zpart), f32(L.dUclip), f32(L.dU), s));
+    VP_HIP(probe_wsum(tokens, bf, (int)B, (int)S, D, H, f32(L.dl), f32(L.fw.zpart), f32(L.dUclip), f32(L.dU), s));
   return VP_OK;
 }
 
