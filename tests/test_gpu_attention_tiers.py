@@ -33,7 +33,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_capped_exp_cpu as cx
+from attention_bar import _merge, _split, _thresholds as _long_thresholds, _unmerge, census, reference_and_bound
 from oracle import videoprism_oracle as orc
 from videoprism import _native as nat
 
@@ -71,77 +71,6 @@ def _for_cap(qkv, heads, cap):
     qkv = qkv.clone()
     qkv[:, :2 * heads * 64] *= float(np.sqrt(cap / 50.0))
     return qkv
-
-
-def _split(qkv, num_seq, S, heads):
-    x = qkv.double().cpu().numpy().reshape(num_seq, S, 3, heads, 64)
-    return [x[:, :, i].transpose(0, 2, 1, 3).reshape(num_seq * heads, S, 64) for i in range(3)]
-
-
-def _merge(o, num_seq, S, heads):
-    return o.reshape(num_seq, heads, S, 64).transpose(0, 2, 1, 3).reshape(num_seq * S, heads * 64)
-
-
-def _unmerge(o, num_seq, S, heads):
-    return o.reshape(num_seq, S, heads, 64).transpose(0, 2, 1, 3).reshape(num_seq * heads, S, 64)
-
-
-def _group_max(a, S):
-    """[P, S, S] -> [P, G, G] maxima over the ballot groups, rows and keys past S clamped to S - 1 as the kernel's
-    loads are (module docstring)."""
-    G = -(-S // 32)
-    idx = np.minimum(np.arange(G * 32), S - 1)
-    a = a[:, idx][:, :, idx]
-    return a.reshape(a.shape[0], G, 32, G, 32).max(axis=(2, 4))
-
-
-def census(q, k, cap, thresholds):
-    """Per ballot group of fp64 logits of the (already rounded) inputs: the largest |x|, the largest accumulation
-    error bound, and the tiers the group may take (a [P, G, G, len(thresholds) + 1] mask: one tier per group, two
-    where the maximum is within the accumulation error of a threshold)."""
-    S = q.shape[1]
-    x = np.matmul(q, k.transpose(0, 2, 1))
-    acc = 64 * 2.0 ** -24 * np.matmul(np.abs(q), np.abs(k).transpose(0, 2, 1))
-    m, a = _group_max(np.abs(x), S), _group_max(acc, S)
-    thr = np.asarray(thresholds, np.float64)
-    lo = (m - a)[..., None] > thr   # certainly past threshold t
-    hi = (m + a)[..., None] > thr   # possibly past it
-    tier_lo, tier_hi = lo.sum(-1), hi.sum(-1)
-    may = (np.arange(len(thr) + 1) >= tier_lo[..., None]) & (np.arange(len(thr) + 1) <= tier_hi[..., None])
-    return x, acc, m, may
-
-
-def _long_thresholds(cap):
-    """0.10 / 0.24 / 0.48 cap as fp32 products (make_cap_poly's x2, x1, x0): written here, not read from the header
-    (tests/test_capped_exp_cpu.py pins the header's), so a moved threshold in the kernel is an error past B."""
-    return [float(np.float32(cx.FACTORS[t]) * np.float32(cap)) for t in ("LIN", "QUAD", "CUBIC")]
-
-
-def _bf16_round(n):
-    """fp64 -> the nearest bf16 value (8 significant bits), ties to even."""
-    m, e = np.frexp(n)
-    return np.ldexp(np.rint(m * 256.0), e - 8)
-
-
-def reference_and_bound(q, k, v, cap):
-    """O and B of the module docstring for [P, S, 64] problems, and the census."""
-    S = q.shape[1]
-    x, acc, m, may = census(q, k, cap, _long_thresholds(cap))
-    bars = [cx.tier_bar(t, cap) + 2.0 ** -23 for t in ("LIN", "QUAD", "CUBIC")]
-    up = lambda g: np.repeat(np.repeat(g, 32, axis=1), 32, axis=2)[:, :S, :S]
-    d = np.zeros_like(x)
-    for t in range(4):
-        bar_t = bars[t] if t < 3 else cx.exact_bar(x, cap)
-        d = np.maximum(d, np.where(up(may[..., t]), bar_t, 0.0))
-    d = d + acc
-    n = np.exp(cap * np.tanh(x / cap))
-    rho = _bf16_round(n)
-    den = n.sum(-1, keepdims=True)
-    O = np.matmul(rho, v) / den
-    flip = (_bf16_round(n * (1 + d)) != rho) | (_bf16_round(n * (1 - d)) != rho)
-    w = (d + flip * 2.0 ** -7) * n
-    B = 2.0 ** -8 * np.abs(O) + (np.matmul(w, np.abs(v)) + np.abs(O) * w.sum(-1, keepdims=True)) / den
-    return O, B, m, may
 
 
 def _counts(may):
