@@ -254,7 +254,8 @@ int vp_op_attention_masked_dh(int precision, const void* qkv, void* o, int64_t n
                               int64_t dim_per_head, float cap, const float* key_pad, int causal, void* stream);
 
 /* video_emb [B, D] . text_emb [Q, D]^T -> out [B, Q] (fp32): the video-text similarity of the
- * LvT models (README / colab usage of FactorizedVideoCLIP's embeddings). */
+ * LvT models (README / colab usage of FactorizedVideoCLIP's embeddings).  One workgroup per (video, text) pair:
+ * meant for a batch's [B, Q] matrix; to search a gallery of embeddings use vp_op_topk below. */
 int vp_op_similarity(const float* video_emb, const float* text_emb, int64_t B, int64_t Q, int64_t D,
                      float* out, void* stream);
 
@@ -410,6 +411,27 @@ int vp_op_probe_forward(const vp_probe_dims* dims, const vp_probe_params* params
 int vp_op_probe_backward(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens, int dtype,
                          int64_t B, int64_t S, const float* dlogits, const vp_probe_grads* grads, void* ws,
                          size_t ws_bytes, void* stream);
+
+/* ---------------- gallery search: fused scores and top-k ----------------
+ * The retrieval step of the LvT models: for each query, the k gallery rows with the largest dot product.  Exact and
+ * deterministic; the [N, Q] score matrix is never formed, the gallery is read once per group of 32 queries (16 where
+ * D > 1024 or k is large), and a score depends on the two vectors alone (not on N, Q, ld, the row's position or the
+ * grid), so a gallery searched in shards and merged gives the bits of the whole search.  Stateless and asynchronous on
+ * `stream`: no allocation, no synchronisation.
+ *   queries  device fp32 [Q, D], contiguous, 16-byte aligned
+ *   gallery  device [N, D] with row stride ld elements (ld >= D, a multiple of 8), VP_F32 or VP_BF16, 16-byte aligned.
+ *            VP_F32: exact fp32 products and sums.  VP_BF16: each query enters as two bf16 terms, so the stored
+ *            gallery's rounding is the only quantisation.  D % 64 == 0, D <= 1536; k <= 128
+ *   scores [Q, k] fp32, ids [Q, k] = id_base + row: score descending, equal scores by ascending id.  A row that scores
+ *            NaN or -inf is never returned; with fewer than k rows the tail is (-inf, -1).  Q == 0 launches nothing.
+ *   ws       vp_op_topk_workspace_bytes(Q, k) bytes (no device needed: the number of row ranges has a fixed bound)
+ * vp_op_topk_merge: the best k <= k_in (<= 128) per query of `parts` lists scores_in / ids_in [parts, Q, k_in], each
+ * in the order above (ids < 0 are padding): the step after per-shard searches with each shard's id_base. */
+int vp_op_topk_workspace_bytes(int64_t Q, int64_t k, size_t* bytes);
+int vp_op_topk(const float* queries, int64_t Q, const void* gallery, int gallery_dtype, int64_t N, int64_t ld, int64_t D,
+               int64_t k, int64_t id_base, float* scores, int64_t* ids, void* ws, size_t ws_bytes, void* stream);
+int vp_op_topk_merge(const float* scores_in, const int64_t* ids_in, int64_t parts, int64_t Q, int64_t k_in, int64_t k,
+                     float* scores, int64_t* ids, void* stream);
 
 /* ---------------- multi-GPU: RCCL all-gather of pooled clip embeddings ----------------
  * The reference runs on one device; its video-text usage scores every clip against every query,

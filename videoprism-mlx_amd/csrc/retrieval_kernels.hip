@@ -1,0 +1,385 @@
+// Exact top-k search of a device-resident gallery of embeddings (vp_op_topk / vp_op_topk_merge; DESIGN.md §4
+// "Gallery search").  Two kernels, no atomics, no [N, Q] matrix:
+//
+// topk_scan_kernel<BF16>: grid (parts, query groups), 512 threads.  A workgroup owns one group of G queries (32, or 16
+// where 32 do not fit the 160 KB of LDS: topk_group) and one contiguous range of gallery rows, which it walks in
+// ascending order in tiles of kTkRows = 512 rows (a wave: 64 rows as two 32-row MFMA tiles).
+//  * Scores: the gallery tile is the A operand and the queries are B, so lane l = (i = l & 31, half = l >> 5) holds
+//    query i's column and acc[q] = score(row (q & 3) + 8 (q >> 2) + 4 half, query i).  A lane loads 16 B of row i per
+//    step straight from memory (the two halves cover 32 B of the row; 4 steps per batch, the next batch in flight under
+//    the MFMAs); the queries sit in LDS in fragment order, written once per workgroup.
+//      fp32 gallery: v_mfma_f32_32x32x2_f32, four per step, element e of the lane's 16 B against the same element of
+//        the query's (k = 8 t + 4 half + e): an exact fmaf chain, the k order permuted alike for every pair.
+//      bf16 gallery: v_mfma_f32_32x32x16_bf16 twice per step, against hi = bf16(q) and then lo = bf16(q - hi): the
+//        gallery's rounding is the only quantisation left.
+//    Every (query, row) pair gets the same instructions in the same order whatever N, Q, ld, the grid, the tile or the
+//    lane, so a score is a function of the two vectors alone.  Rows past the range are never read (their lanes load
+//    nothing and multiply zeros) and never selected.
+//  * Selection: each query's best k so far in LDS, unordered but for the last slot, which holds the worst of them (the
+//    k-th score).  A lane compares its 32 accumulators with its query's k-th score; a wave whose ballot finds no better
+//    score is done with the tile.  Otherwise the waves insert one after the other (rows ascend from wave to wave), each
+//    wave row by row (a ballot per 8 rows, then per row): a lane holding a better score overwrites the worst entry,
+//    finds the new worst in one pass over the list and both of the query's lanes re-read it; the list is ordered once,
+//    by counting, when it is written out.  Rows arrive in ascending
+//    order, so `score > k-th` is the whole order rule: an equal score with a larger id never displaces, and a NaN or
+//    -inf compares false against the initial -inf.  Expected inserts per query and range: about k ln(n / k).
+//  * Output: lists [part][Q][k] of (score, id_base + row), padded with (-inf, -1).
+//
+// topk_merge_kernel: one workgroup per query merges `parts` sorted lists into the best k: L - 1 lists at a time join the
+// running result in LDS and a tree of pairwise merges halves them; an element's place in a pair's output is its index
+// plus the number of the other list's elements that come before it (binary search; on a full tie the even list first),
+// so every output slot is written by exactly one thread.  The order (score descending, id ascending, padding last) is
+// total, which makes the result independent of how the rows were split into lists.
+#include "vp_common.h"
+#include "vp_kernels.h"
+
+#include <cmath>
+
+namespace vp {
+
+namespace {
+
+constexpr int kTkWaves = 8;              // two per SIMD: the loads in flight, not the LDS, set the streaming rate
+constexpr int kTkThreads = 64 * kTkWaves;
+constexpr int kTkRows = 64 * kTkWaves;   // rows of a workgroup's tile: each wave 2 MFMA tiles of 32
+constexpr int kTkLdsBytes = 160 * 1024;  // LDS of a CU; one workgroup may take all of it
+constexpr uint32_t kTkNoRow = 0xffffffffu;
+
+__device__ __forceinline__ uint32_t pack_bf2(bf16_t a, bf16_t b) {
+  return (uint32_t)__builtin_bit_cast(uint16_t, a) | ((uint32_t)__builtin_bit_cast(uint16_t, b) << 16);
+}
+
+// 8 fp32 query values -> their 8 bf16 hi terms and 8 bf16 lo terms (q ~ hi + lo to about 2^-16 relative)
+__device__ __forceinline__ void split8(const float (&v)[8], f32x4& hi, f32x4& lo) {
+  uint32_t h[4], l[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const bf16_t h0 = f2bf(v[2 * e]), h1 = f2bf(v[2 * e + 1]);
+    h[e] = pack_bf2(h0, h1);
+    l[e] = pack_bf2(f2bf(v[2 * e] - bf2f(h0)), f2bf(v[2 * e + 1] - bf2f(h1)));
+  }
+  hi = f32x4{__uint_as_float(h[0]), __uint_as_float(h[1]), __uint_as_float(h[2]), __uint_as_float(h[3])};
+  lo = f32x4{__uint_as_float(l[0]), __uint_as_float(l[1]), __uint_as_float(l[2]), __uint_as_float(l[3])};
+}
+
+// one batch of 4 steps for the wave's two row tiles; lanes of rows past the range load nothing
+__device__ __forceinline__ void tk_load(f32x4 (&a)[2][4], const char* const (&rp)[2], const bool (&ok)[2], int t) {
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      a[rt][u] = ok[rt] ? *reinterpret_cast<const f32x4*>(rp[rt] + (int64_t)(t + u) * 32) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+template <bool BF16>
+__device__ __forceinline__ void tk_mma(const f32x4 (&a)[2][4], const f32x4* bq, int t, int G, int i, int half,
+                                       bool qlane, f32x16 (&acc)[2]) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int s = t + u;
+    if constexpr (BF16) {
+      const f32x4 bh = qlane ? bq[((s * 2 + 0) * 2 + half) * G + i] : zero;
+      const f32x4 bl = qlane ? bq[((s * 2 + 1) * 2 + half) * G + i] : zero;
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        const bf16x8 av = __builtin_bit_cast(bf16x8, a[rt][u]);
+        acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8, bh), acc[rt], 0, 0, 0);
+        acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8, bl), acc[rt], 0, 0, 0);
+      }
+    } else {
+      const f32x4 b = qlane ? bq[(s * 2 + half) * G + i] : zero;
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+          acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[rt][u][e], b[e], acc[rt], 0, 0, 0);
+    }
+  }
+}
+
+// The wave's rows that beat their query's k-th score enter its list, in row order (see the file comment).
+__device__ __forceinline__ void tk_insert(const f32x16 (&acc)[2], int64_t r0, int64_t p0, int64_t p1, int k, int i,
+                                          int half, bool qlane, float* lsc, uint32_t* lid) {
+  float* sc = lsc + i * k;
+  uint32_t* id = lid + i * k;
+  __threadfence_block();
+  float thr = qlane ? sc[k - 1] : INFINITY;
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt) {
+#pragma unroll
+    for (int qb = 0; qb < 4; ++qb) {  // rows 8 qb .. 8 qb + 7 of the tile: acc[4 qb .. 4 qb + 3] of both halves
+      bool c4 = false;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) c4 |= r0 + 32 * rt + 8 * qb + 4 * half + e < p1 && acc[rt][4 * qb + e] > thr;
+      if (__ballot(c4) == 0) continue;
+#pragma unroll
+      for (int jj = 8 * qb; jj < 8 * qb + 8; ++jj) {
+        const int q = (jj & 3) + 4 * (jj >> 3);  // row jj is acc[q] of the lanes with half == (jj >> 2) & 1
+        const int64_t row = r0 + 32 * rt + jj;
+        const float v = acc[rt][q];
+        const bool c = half == ((jj >> 2) & 1) && row < p1 && v > thr;
+        if (__ballot(c) != 0) {
+          if (c) {
+            // the new entry evicts slot k - 1, the worst; the worst of the k now there (lowest score, of equal scores
+            // the largest row) trades places with it
+            const uint32_t rr = (uint32_t)(row - p0);
+            float ws = v;
+            uint32_t wr = rr;
+            int wp = k - 1;
+            for (int p = 0; p < k - 1; ++p) {
+              const float s = sc[p];
+              const uint32_t r = id[p];
+              if (s < ws || (s == ws && r > wr)) ws = s, wr = r, wp = p;
+            }
+            sc[wp] = v;
+            id[wp] = rr;
+            sc[k - 1] = ws;
+            id[k - 1] = wr;
+          }
+          __threadfence_block();  // the query's other half-lane reads the new k-th score
+          thr = qlane ? sc[k - 1] : INFINITY;
+        }
+      }
+    }
+  }
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __restrict__ queries, int64_t Q,
+                                                        const void* __restrict__ gallery, int64_t N, int64_t ld, int D,
+                                                        int k, int G, int64_t rows_per_part, int64_t id_base,
+                                                        float* __restrict__ ws_sc, int64_t* __restrict__ ws_id) {
+  extern __shared__ __attribute__((aligned(16))) char tk_smem[];
+  f32x4* bq = reinterpret_cast<f32x4*>(tk_smem);                          // D * G * 4 bytes, fragment order
+  float* lsc = reinterpret_cast<float*>(tk_smem + (size_t)D * G * 4);     // [G][k]
+  uint32_t* lid = reinterpret_cast<uint32_t*>(lsc + G * k);               // [G][k] row - p0
+  volatile int* flags = reinterpret_cast<volatile int*>(lid + G * k);     // [2][kTkWaves]
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, w = tid >> 6, i = lane & 31, half = lane >> 5;
+  const int64_t q0 = (int64_t)blockIdx.y * G;
+
+  for (int e = tid; e < G * k; e += kTkThreads) {
+    lsc[e] = -INFINITY;
+    lid[e] = kTkNoRow;
+  }
+  if constexpr (BF16) {
+    const int nc = D >> 3;  // chunks of 8 values: step c >> 1, half c & 1
+    for (int e = tid; e < G * nc; e += kTkThreads) {
+      const int qi = e / nc, c = e % nc;
+      float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (q0 + qi < Q) {
+        const float4* src = reinterpret_cast<const float4*>(queries + (q0 + qi) * D + 8 * c);
+        const float4 x = src[0], y = src[1];
+        v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w, v[4] = y.x, v[5] = y.y, v[6] = y.z, v[7] = y.w;
+      }
+      f32x4 hi, lo;
+      split8(v, hi, lo);
+      const int s = c >> 1, h = c & 1;
+      bq[((s * 2 + 0) * 2 + h) * G + qi] = hi;
+      bq[((s * 2 + 1) * 2 + h) * G + qi] = lo;
+    }
+  } else {
+    const int nc = D >> 2;  // chunks of 4 values
+    for (int e = tid; e < G * nc; e += kTkThreads) {
+      const int qi = e / nc, c = e % nc;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (q0 + qi < Q) v = *reinterpret_cast<const f32x4*>(queries + (q0 + qi) * D + 4 * c);
+      bq[((c >> 1) * 2 + (c & 1)) * G + qi] = v;
+    }
+  }
+  __syncthreads();
+
+  const int64_t p0 = (int64_t)blockIdx.x * rows_per_part;
+  const int64_t p1 = p0 + rows_per_part < N ? p0 + rows_per_part : N;
+  const int64_t row_bytes = ld * (BF16 ? 2 : 4);
+  const int nt = (D * (BF16 ? 2 : 4)) >> 5;  // 32-byte steps of a row: a multiple of 4
+  const bool qlane = i < G;
+  int par = 0;
+  for (int64_t tb = p0; tb < p1; tb += kTkRows, par ^= 1) {
+    const int64_t r0 = tb + 64 * w;
+    f32x16 acc[2] = {};
+    if (r0 < p1) {  // whole wave
+      const char* rp[2];
+      bool ok[2];
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        const int64_t row = r0 + 32 * rt + i;
+        ok[rt] = row < p1;
+        rp[rt] = static_cast<const char*>(gallery) + row * row_bytes + 16 * half;
+      }
+      f32x4 a0[2][4], a1[2][4];
+      tk_load(a0, rp, ok, 0);
+      for (int t = 0; t < nt; t += 8) {
+        const bool more = t + 4 < nt;
+        if (more) tk_load(a1, rp, ok, t + 4);
+        tk_mma<BF16>(a0, bq, t, G, i, half, qlane, acc);
+        if (more) {
+          if (t + 8 < nt) tk_load(a0, rp, ok, t + 8);
+          tk_mma<BF16>(a1, bq, t + 4, G, i, half, qlane, acc);
+        }
+      }
+    }
+    // lists last changed before the previous tile's final barrier
+    const float thr = qlane ? lsc[i * k + k - 1] : INFINITY;
+    bool any = false;
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int64_t row = r0 + 32 * rt + (q & 3) + 8 * (q >> 2) + 4 * half;
+        any |= row < p1 && acc[rt][q] > thr;
+      }
+    const bool wany = __ballot(any) != 0;
+    if (lane == 0) flags[par * kTkWaves + w] = wany;
+    __syncthreads();
+#pragma unroll
+    for (int ww = 0; ww < kTkWaves; ++ww) {
+      if (flags[par * kTkWaves + ww]) {  // the same for every thread
+        if (w == ww) tk_insert(acc, r0, p0, p1, k, i, half, qlane, lsc, lid);
+        __syncthreads();
+      }
+    }
+  }
+  __syncthreads();
+  const int64_t part = blockIdx.x;
+  for (int e = tid; e < G * k; e += kTkThreads) {
+    const int qi = e / k, j = e % k;
+    if (q0 + qi >= Q) continue;
+    // the lists are unordered but for their last slot: an entry goes where the count of entries that beat it says
+    // (score descending, row ascending; among the padding, slot order)
+    const float s = lsc[e];
+    const uint32_t r = lid[e];
+    int rank = 0;
+    for (int p = 0; p < k; ++p) {
+      const float s2 = lsc[qi * k + p];
+      const uint32_t r2 = lid[qi * k + p];
+      rank += s2 > s || (s2 == s && (r2 < r || (r2 == r && p < j)));
+    }
+    const int64_t o = (part * Q + q0 + qi) * k + rank;
+    ws_sc[o] = s;
+    ws_id[o] = r == kTkNoRow ? (int64_t)-1 : id_base + p0 + (int64_t)r;
+  }
+}
+
+// the order: score descending, id ascending, padding (id < 0) last
+__device__ __forceinline__ bool tk_beats(float s1, int64_t i1, float s2, int64_t i2) {
+  if (i1 < 0) return false;
+  if (i2 < 0) return true;
+  return s1 > s2 || (s1 == s2 && i1 < i2);
+}
+
+__global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict__ sin, const int64_t* __restrict__ iin,
+                                                         int64_t parts, int64_t Q, int k_in, int k, int L,
+                                                         float* __restrict__ so, int64_t* __restrict__ io) {
+  extern __shared__ __attribute__((aligned(16))) char mg_smem[];
+  // two buffers of L lists of k_in entries
+  int64_t* idb = reinterpret_cast<int64_t*>(mg_smem);
+  float* scb = reinterpret_cast<float*>(idb + 2 * L * k_in);
+  const int tid = threadIdx.x;
+  const int64_t q = blockIdx.x;
+  const int LK = L * k_in;
+  int cur = 0;
+  for (int e = tid; e < k_in; e += 256) {  // list 0: the running result
+    scb[e] = -INFINITY;
+    idb[e] = -1;
+  }
+  for (int64_t base = 0; base < parts; base += L - 1) {
+    for (int e = tid; e < LK - k_in; e += 256) {
+      const int64_t p = base + e / k_in;
+      float s = -INFINITY;
+      int64_t id = -1;
+      if (p < parts) {
+        const int64_t o = (p * Q + q) * k_in + e % k_in;
+        s = sin[o];
+        id = iin[o];
+        if (!(s > -INFINITY) || id < 0) s = -INFINITY, id = -1;  // NaN and -inf never rank
+      }
+      scb[cur * LK + k_in + e] = s;
+      idb[cur * LK + k_in + e] = id;
+    }
+    __syncthreads();
+    for (int n = L; n > 1; n >>= 1) {
+      const float* cs = scb + cur * LK;
+      const int64_t* ci = idb + cur * LK;
+      float* ns = scb + (cur ^ 1) * LK;
+      int64_t* ni = idb + (cur ^ 1) * LK;
+      for (int e = tid; e < n * k_in; e += 256) {
+        const int l = e / k_in, j = e % k_in;
+        const float s = cs[e];
+        const int64_t id = ci[e];
+        const float* os = cs + (l ^ 1) * k_in;
+        const int64_t* oi = ci + (l ^ 1) * k_in;
+        int lo = 0, hi = k_in;  // entries of the other list that come before this one
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          const bool before = (l & 1) ? !tk_beats(s, id, os[mid], oi[mid]) : tk_beats(os[mid], oi[mid], s, id);
+          if (before) lo = mid + 1;
+          else hi = mid;
+        }
+        const int rank = j + lo;
+        if (rank < k_in) {
+          ns[(l >> 1) * k_in + rank] = s;
+          ni[(l >> 1) * k_in + rank] = id;
+        }
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < k; e += 256) {
+    so[q * k + e] = scb[cur * LK + e];
+    io[q * k + e] = idb[cur * LK + e];
+  }
+}
+
+}  // namespace
+
+int topk_group(int D, int k) {
+  return D <= 1024 && (size_t)D * 32 * 4 + (size_t)32 * k * 8 + 64 <= (size_t)kTkLdsBytes ? 32 : 16;
+}
+
+hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D, int k,
+                     int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s) {
+  if (Q < 1 || N < 0 || D < 64 || D % 64 || D > kPoolMaxD || k < 1 || k > kTopkMaxK || ld < D) return hipErrorInvalidValue;
+  const int G = topk_group(D, k);
+  const int64_t groups = (Q + G - 1) / G;
+  if (groups > 65535) return hipErrorInvalidValue;
+  // about one workgroup per CU (each takes most of a CU's LDS), every range a whole number of tiles
+  const int64_t tiles = (N + kTkRows - 1) / kTkRows;
+  int64_t parts = device_cu_count() / groups;
+  parts = parts < 1 ? 1 : parts > kTopkMaxParts ? kTopkMaxParts : parts;
+  parts = tiles < 1 ? 1 : parts > tiles ? tiles : parts;
+  const int64_t rows_per_part = tiles < 1 ? kTkRows : (tiles + parts - 1) / parts * kTkRows;
+  if (rows_per_part >= (int64_t)kTkNoRow) return hipErrorInvalidValue;
+  parts = tiles < 1 ? 1 : (N + rows_per_part - 1) / rows_per_part;
+  const int lds = D * G * 4 + G * k * 8 + 2 * kTkWaves * 4;
+  const void* fn = bf16 ? reinterpret_cast<const void*>(&topk_scan_kernel<true>)
+                        : reinterpret_cast<const void*>(&topk_scan_kernel<false>);
+  hipError_t e = ensure_dyn_lds(fn, kTkLdsBytes);
+  if (e != hipSuccess) return e;
+  const dim3 grid((unsigned)parts, (unsigned)groups);
+  if (bf16)
+    hipLaunchKernelGGL(topk_scan_kernel<true>, grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N, ld, D, k, G,
+                       rows_per_part, id_base, ws_sc, ws_id);
+  else
+    hipLaunchKernelGGL(topk_scan_kernel<false>, grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N, ld, D, k, G,
+                       rows_per_part, id_base, ws_sc, ws_id);
+  *parts_out = (int)parts;
+  return hipGetLastError();
+}
+
+hipError_t topk_merge(const float* sin, const int64_t* iin, int64_t parts, int64_t Q, int k_in, int k, float* so,
+                      int64_t* io, hipStream_t s) {
+  if (parts < 1 || Q < 1 || Q > 0x7fffffff || k_in < 1 || k_in > kTopkMaxK || k < 1 || k > k_in)
+    return hipErrorInvalidValue;
+  // as many lists at a time as 48 KB of LDS hold twice (16 at k_in = 128), no more than there are
+  int L = 2;
+  while (L < 256 && L < parts + 1 && (size_t)2 * (2 * L) * k_in * 12 <= 48 * 1024) L *= 2;
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), (size_t)2 * L * k_in * 12, s, sin, iin, parts, Q,
+                     k_in, k, L, so, io);
+  return hipGetLastError();
+}
+
+}  // namespace vp

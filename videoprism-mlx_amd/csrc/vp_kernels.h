@@ -271,6 +271,20 @@ hipError_t probe_fold_bwd(const float* dU, const float* qt, int D, int H, float*
 hipError_t probe_dq(const float* dqt, const float* qraw, const float* pds, int D, int H, float* dqraw, float* dpds,
                     hipStream_t s);
 
+// ---- gallery search (retrieval_kernels.hip) ----
+constexpr int kTopkMaxK = 128;      // longest list a query keeps
+constexpr int kTopkMaxParts = 256;  // most row ranges a search splits the gallery into (sizes the workspace)
+// queries of a workgroup: 32, or 16 where 32 (with their lists) do not fit the LDS; scores do not depend on it
+int topk_group(int D, int k);
+// pass 1: per row range p < *parts_out (<= kTopkMaxParts) the best k of rows [p * n, (p + 1) * n) per query, sorted by
+// (score descending, row ascending) and padded with (-inf, -1): ws_sc / ws_id [parts][Q][k], ids = id_base + row.
+// queries fp32 [Q][D]; gallery fp32 or bf16 [N][ld]; D = 64 j <= kPoolMaxD; N = 0 gives one list of padding
+hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D, int k,
+                     int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s);
+// pass 2: the best k <= k_in of `parts` such lists [parts][Q][k_in] per query, same order, ties between lists by id
+hipError_t topk_merge(const float* sin, const int64_t* iin, int64_t parts, int64_t Q, int k_in, int k, float* so,
+                      int64_t* io, hipStream_t s);
+
 // ---- frame ingest (preprocess.hip) ----
 // video_utils.py:109-124: size of the resized frame and the crop window's origin in it (mode 0 centre
 // crop, 1 stretch to S x S); a message if this library's kernel cannot take the geometry, else nullptr

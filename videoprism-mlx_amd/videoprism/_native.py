@@ -199,6 +199,14 @@ _SIGNATURES = {
                                     c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vp_op_probe_backward": (c_int, [POINTER(vp_probe_dims), POINTER(vp_probe_params), c_void_p, c_int, c_int64,
                                      c_int64, c_void_p, POINTER(vp_probe_params), c_void_p, c_size_t, c_void_p]),
+    # gallery search: fused scores and top-k (videoprism/retrieval.py)
+    "vp_op_topk_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "vp_op_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_op_topk_merge": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                 c_void_p]),
+    # not in the public header: queries per workgroup of the search at (D, k) (tools/retrieval_bench.py); no GPU call
+    "vp_dev_topk_group": (c_int, [c_int64, c_int64]),
     # not in the public header: one streaming pass of the backward on its own (tools/probe_bench.py)
     "vp_dev_probe_backward_pass": (c_int, [POINTER(vp_probe_dims), c_void_p, c_int, c_int64, c_int64, c_int, c_void_p,
                                            c_size_t, c_void_p]),
@@ -639,6 +647,51 @@ def op_similarity(video_emb, text_emb, stream=None):
     out = torch.empty((B, Q), dtype=torch.float32, device=video_emb.device)
     call("vp_op_similarity", _ptr(video_emb), _ptr(text_emb), B, Q, D, _ptr(out), _stream(stream))
     return out
+
+
+def op_topk_workspace_bytes(Q, k) -> int:
+    n = c_size_t()
+    call("vp_op_topk_workspace_bytes", Q, k, ctypes.byref(n))
+    return n.value
+
+
+def op_topk(queries, gallery, k, id_base=0, stream=None, ws=None):
+    """The k rows of gallery [N, D] (fp32 or bf16, unit row stride along D, any row stride) with the largest dot
+    product per row of queries [Q, D] (fp32): (scores [Q, k] fp32, ids [Q, k] int64 = id_base + row), score
+    descending and equal scores by ascending id; fewer than k rows leave (-inf, -1).  `ws`: uint8 workspace of
+    op_topk_workspace_bytes(Q, k) bytes (allocated when None)."""
+    import torch
+    Q, D = queries.shape
+    N = gallery.shape[0]
+    if gallery.dim() != 2 or gallery.shape[1] != D or (N > 1 and gallery.stride(1) != 1):
+        raise ValueError(f"gallery must be [N, {D}] with contiguous rows, got {tuple(gallery.shape)}")
+    if queries.dtype != torch.float32:
+        raise TypeError("queries must be fp32")
+    queries = queries.contiguous()
+    ld = gallery.stride(0) if N > 1 else D
+    scores = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    if Q == 0:
+        return scores, ids
+    if ws is None:
+        ws = torch.empty(op_topk_workspace_bytes(Q, k), dtype=torch.uint8, device=queries.device)
+    with torch.cuda.device(queries.device):  # no handle: the op launches on the current device
+        call("vp_op_topk", _ptr(queries), Q, _ptr(gallery), _prec(gallery), N, ld, D, k, id_base, _ptr(scores),
+             _ptr(ids), _ptr(ws), ws.numel(), _stream(stream))
+    return scores, ids
+
+
+def op_topk_merge(scores, ids, k, stream=None):
+    """The best k per query of sorted lists scores / ids [parts, Q, k_in] (op_topk's order; ids < 0 are padding)."""
+    import torch
+    parts, Q, k_in = scores.shape
+    scores, ids = scores.contiguous(), ids.contiguous()
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=scores.device)
+    out_i = torch.empty((Q, k), dtype=torch.int64, device=scores.device)
+    with torch.cuda.device(scores.device):
+        call("vp_op_topk_merge", _ptr(scores), _ptr(ids), parts, Q, k_in, k, _ptr(out_s), _ptr(out_i),
+             _stream(stream))
+    return out_s, out_i
 
 
 def op_layernorm(x, gamma1p, beta, out_dtype=None, perm=PERM_NONE, T=1, Nsp=1, add=None,
