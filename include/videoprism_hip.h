@@ -234,6 +234,39 @@ int vp_op_preprocess_frames(const uint8_t* src, int64_t N, int64_t H, int64_t W,
                             int64_t frame_stride, const int32_t* frame_idx, int64_t F, int mode,
                             int swap_rb, int64_t S, uint8_t* dst, void* stream);
 
+/* The same step in front of a decoder's 4:2:0 surfaces, read in place (no decoder is part of this library).
+ *   VP_YUV_NV12  8-bit: a Y plane and one plane of interleaved U,V byte pairs
+ *   VP_YUV_I420  8-bit: separate Y, U and V planes
+ *   VP_YUV_P010  NV12's layout in little-endian 16-bit words; the 10-bit sample is word >> 6
+ * The Y plane is H x W samples, the chroma planes ceil(H/2) x ceil(W/2) (pairs, when interleaved): odd H
+ * and W are legal.  Plane p holds frame n, row y at plane[p] + n*frame_stride[p] + y*row_stride[p]; no
+ * byte outside those rows is read.  P010 bases and strides must be multiples of 2. */
+enum vp_yuv_format { VP_YUV_NV12 = 0, VP_YUV_I420 = 1, VP_YUV_P010 = 2 };
+enum vp_yuv_matrix { VP_YUV_BT601 = 0, VP_YUV_BT709 = 1 };
+enum vp_yuv_range  { VP_YUV_LIMITED = 0, VP_YUV_FULL = 1 };
+typedef struct {
+  const void* plane[3];        /* Y, UV, NULL (NV12, P010) or Y, U, V (I420): device pointers */
+  int64_t row_stride[3];       /* bytes */
+  int64_t frame_stride[3];     /* bytes */
+  int format, matrix, range;
+} vp_yuv_frames;
+
+/* dst = vp_op_preprocess_frames applied to the full-resolution RGB frame that is never stored: each tap
+ * is converted to uint8 R, G, B first, then blended.  Chroma is not interpolated: luma (y, x) uses chroma
+ * sample (y >> 1, x >> 1).  The conversion is 16.16 fixed point, clamped once at the end:
+ *   out = clip((cy*(Y - yoff) + cu*(U - coff) + cv*(V - coff) + 32768) >> 16, 0, 255)
+ * with the coefficients of vp_dev_yuv_coefficients (tests/yuv_restatement.py states it).  N, H, W, frame_idx,
+ * F, mode, S, dst (R, G, B order) and the geometry limits are vp_op_preprocess_frames'.  Asynchronous on
+ * `stream` on the current device; never allocates, never synchronises; argument errors are VP_EINVAL
+ * before any device call. */
+int vp_op_preprocess_yuv(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t W, const int32_t* frame_idx,
+                         int64_t F, int mode, int64_t S, uint8_t* dst, void* stream);
+
+/* The integer table vp_op_preprocess_yuv uses: out[0..8] = rows R, G, B x (cy, cu, cv), each
+ * floor(x * 65536 + 0.5) of the real coefficient, out[9] = yoff, out[10] = coff; bit_depth 8 or 10.
+ * No device needed. */
+int vp_dev_yuv_coefficients(int matrix, int range, int bit_depth, int32_t out[11]);
+
 /* Build-defined pooled clip embedding used by the multi-GPU gather (the video-only encoder
  * has no pooler in the reference): out[b] = l2norm(mean_l emb[b, l, :]) in fp32, with the
  * reference's _l2_normalize (encoders.py:50-67, eps 1e-12). */

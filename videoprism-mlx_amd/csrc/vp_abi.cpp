@@ -908,6 +908,56 @@ int vp_op_preprocess_frames(const uint8_t* src, int64_t N, int64_t H, int64_t W,
   return VP_OK;
 }
 
+int vp_dev_yuv_coefficients(int matrix, int range, int bit_depth, int32_t out[11]) {
+  if (!out) return fail(VP_EINVAL, "null argument");
+  if (const char* why = vp::yuv_coefficients(matrix, range, bit_depth, out)) return fail(VP_EINVAL, why);
+  return VP_OK;
+}
+
+int vp_op_preprocess_yuv(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t W, const int32_t* frame_idx,
+                         int64_t F, int mode, int64_t S, uint8_t* dst, void* stream) {
+  using namespace vp;
+  if (!src || !src->plane[0] || !dst) return fail(VP_EINVAL, "null argument");
+  const int fmt = src->format;
+  if (fmt != VP_YUV_NV12 && fmt != VP_YUV_I420 && fmt != VP_YUV_P010)
+    return fail(VP_EINVAL, "Unknown pixel format: " + std::to_string(fmt));
+  int32_t coef[11];
+  if (const char* why = yuv_coefficients(src->matrix, src->range, fmt == VP_YUV_P010 ? 10 : 8, coef))
+    return fail(VP_EINVAL, why);
+  const int planes = fmt == VP_YUV_I420 ? 3 : 2;
+  for (int p = 1; p < planes; ++p)
+    if (!src->plane[p]) return fail(VP_EINVAL, "missing chroma plane");
+  if (N < 1 || H < 1 || W < 1 || F < 1 || S < 1) return fail(VP_EINVAL, "N, H, W, F and S must be at least 1");
+  if (mode != VP_RESIZE_CENTER_CROP && mode != VP_RESIZE_STRETCH)
+    return fail(VP_EINVAL, "Unknown resize_mode: " + std::to_string(mode));
+  if (H >= (1 << 24) || W >= (1 << 24) || S > 16384 || N > INT32_MAX || F > INT32_MAX)
+    return fail(VP_EINVAL, "frame geometry out of range (H, W < 2^24, S <= 16384, N, F < 2^31)");
+  const int64_t sample = fmt == VP_YUV_P010 ? 2 : 1, ch = (H + 1) / 2, cw = (W + 1) / 2;
+  YuvPlanes pl;
+  pl.format = fmt;
+  for (int p = 0; p < 3; ++p) {
+    pl.plane[p] = p < planes ? src->plane[p] : nullptr;
+    pl.row_stride[p] = p < planes ? src->row_stride[p] : 0;
+    pl.frame_stride[p] = p < planes ? src->frame_stride[p] : 0;
+    if (p >= planes) continue;
+    const int64_t rows = p ? ch : H, row_bytes = (p == 0 ? W : fmt == VP_YUV_I420 ? cw : 2 * cw) * sample;
+    if (pl.row_stride[p] < row_bytes)
+      return fail(VP_EINVAL, "row_stride[" + std::to_string(p) + "] must be at least " + std::to_string(row_bytes) + " bytes");
+    if (pl.frame_stride[p] < rows * pl.row_stride[p])
+      return fail(VP_EINVAL, "frame_stride[" + std::to_string(p) + "] must be at least its rows times row_stride bytes");
+    if (fmt == VP_YUV_P010 && (((uintptr_t)pl.plane[p] | (uintptr_t)pl.row_stride[p] | (uintptr_t)pl.frame_stride[p]) & 1))
+      return fail(VP_EINVAL, "P010 plane bases and strides must be multiples of 2 bytes");
+  }
+  if (!frame_idx && F > N)
+    return fail(VP_EINVAL, "Video has only " + std::to_string(N) + " frames, but " + std::to_string(F) + " requested");
+  int64_t nh, nw, y0, x0;
+  if (const char* why = preprocess_geometry(H, W, S, mode, &nh, &nw, &y0, &x0)) return fail(VP_EINVAL, why);
+  hipError_t e = preprocess_yuv(pl, coef, N, H, W, frame_idx, F, mode, S, dst, static_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) return fail(VP_EINVAL, "too many output pixels for one launch");
+  VP_HIP(e);
+  return VP_OK;
+}
+
 int vp_op_pool_l2(const void* emb, int dtype, int64_t B, int64_t L, int64_t D, float* out,
                   void* stream) {
   using namespace vp;

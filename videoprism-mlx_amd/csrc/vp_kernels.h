@@ -295,5 +295,19 @@ const char* preprocess_geometry(int64_t H, int64_t W, int64_t S, int mode, int64
 hipError_t preprocess_frames(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
                              int64_t frame_stride, const int32_t* frame_idx, int64_t F, int mode, int swap_rb,
                              int64_t S, uint8_t* dst, hipStream_t s);
+// The same from a decoder's 4:2:0 planes (the values of vp_yuv_format): the taps are converted to uint8 RGB
+// on the way, luma (y, x) with chroma (y >> 1, x >> 1), then resized as above.
+enum { YUV_NV12 = 0, YUV_I420 = 1, YUV_P010 = 2 };
+struct YuvPlanes {
+  const void* plane[3];                    // Y, UV, - (NV12, P010: 16-bit words) or Y, U, V (I420)
+  int64_t row_stride[3], frame_stride[3];  // bytes
+  int format;
+};
+// out[0..8] = rows R, G, B x (cy, cu, cv) = floor(x * 65536 + 0.5), out[9] = yoff, out[10] = coff for
+// matrix 0 (BT.601) / 1 (BT.709), range 0 (limited) / 1 (full), bit_depth 8 / 10; a message for anything else
+const char* yuv_coefficients(int matrix, int range, int bit_depth, int32_t out[11]);
+// coef: yuv_coefficients' table.  P010 planes and strides must be 2-byte aligned (hipErrorInvalidValue)
+hipError_t preprocess_yuv(const YuvPlanes& src, const int32_t coef[11], int64_t N, int64_t H, int64_t W,
+                          const int32_t* frame_idx, int64_t F, int mode, int64_t S, uint8_t* dst, hipStream_t s);
 
 }  // namespace vp

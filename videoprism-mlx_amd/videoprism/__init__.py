@@ -9,4 +9,4 @@ C-ABI in include/videoprism_hip.h) loaded through `videoprism._native`.
 __version__ = "0.1.0"
 
 from . import video_utils  # noqa: E402,F401
-from .video_utils import load_video, load_video_batch, preprocess_frames  # noqa: E402,F401
+from .video_utils import load_video, load_video_batch, preprocess_frames, preprocess_yuv_frames  # noqa: E402,F401

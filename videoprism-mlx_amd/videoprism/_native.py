@@ -25,6 +25,9 @@ EPI_STORE, EPI_GELU, EPI_RESID, EPI_POS, EPI_RESID_FFN = 0, 1, 2, 3, 4
 EPI_RESID_BF16, EPI_POS_BF16, EPI_RESID_FFN_BF16 = 5, 6, 7
 PERM_NONE, PERM_BTN_TO_BNT, PERM_BNT_TO_BTN = 0, 1, 2
 VP_RESIZE_CENTER_CROP, VP_RESIZE_STRETCH = 0, 1
+VP_YUV_NV12, VP_YUV_I420, VP_YUV_P010 = 0, 1, 2
+VP_YUV_BT601, VP_YUV_BT709 = 0, 1
+VP_YUV_LIMITED, VP_YUV_FULL = 0, 1
 
 
 class NativeLibraryError(RuntimeError):
@@ -94,6 +97,11 @@ class vp_probe_params(ctypes.Structure):  # device fp32 pointers; vp_probe_grads
     _fields_ = [(member, c_void_p) for member, _ in PROBE_LEAVES]
 
 
+class vp_yuv_frames(ctypes.Structure):  # device planes Y, UV, - (NV12, P010) or Y, U, V (I420); strides in bytes
+    _fields_ = [("plane", c_void_p * 3), ("row_stride", c_int64 * 3), ("frame_stride", c_int64 * 3),
+                ("format", c_int), ("matrix", c_int), ("range", c_int)]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "vp_last_error": (c_char_p, []),
@@ -158,6 +166,10 @@ _SIGNATURES = {
                                c_int64, c_int64, c_void_p]),
     "vp_op_preprocess_frames": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                         c_int64, c_int, c_int, c_int64, c_void_p, c_void_p]),
+    "vp_op_preprocess_yuv": (c_int, [POINTER(vp_yuv_frames), c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
+                                     c_int64, c_void_p, c_void_p]),
+    # the conversion's integer table (tests/yuv_restatement.py); no GPU call
+    "vp_dev_yuv_coefficients": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
     "vp_op_pool_l2": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "vp_op_attention_masked": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float,
                                        c_void_p, c_int, c_void_p]),
@@ -823,3 +835,66 @@ def profile_kernel_name(handle, cls_name: str) -> str:
             call("vp_profile_kernel_name", handle, i, ctypes.byref(k))
             return kernel_short_name(k.value.decode()) if k.value else ""
     return ""
+
+
+def yuv_coefficients(matrix, color_range, bit_depth):
+    """The 16.16 table of vp_op_preprocess_yuv: (int32 [3][3] rows R, G, B x (cy, cu, cv), yoff, coff)."""
+    out = (c_int32 * 11)()
+    call("vp_dev_yuv_coefficients", int(matrix), int(color_range), int(bit_depth), out)
+    v = list(out)
+    return [v[0:3], v[3:6], v[6:9]], v[9], v[10]
+
+
+def yuv_frames(planes, pixel_format=VP_YUV_NV12, matrix=VP_YUV_BT601, color_range=VP_YUV_LIMITED):
+    """(vp_yuv_frames, N, H, W) of device planes, which the struct points into: (y [N, H, W],
+    uv [N, ceil(H/2), ceil(W/2), 2]) for NV12 (uint8) and P010 (int16 / uint16 words), (y, u [N, ceil(H/2),
+    ceil(W/2)], v) for I420, with any frame and row strides (only the sample, or the U,V pair, must be contiguous)."""
+    import torch
+    nplanes = {VP_YUV_NV12: 2, VP_YUV_I420: 3, VP_YUV_P010: 2}.get(pixel_format)
+    if nplanes is None:
+        raise ValueError(f"Unknown pixel format: {pixel_format}")
+    if len(planes) != nplanes:
+        raise ValueError(f"pixel format {pixel_format} takes {nplanes} planes, got {len(planes)}")
+    words = (torch.uint16, torch.int16) if pixel_format == VP_YUV_P010 else (torch.uint8,)
+    y = planes[0]
+    if y.dim() != 3:
+        raise ValueError(f"the Y plane must be [N, H, W], got {tuple(y.shape)}")
+    N, H, W = y.shape
+    chroma = (N, (H + 1) // 2, (W + 1) // 2) + ((2,) if nplanes == 2 else ())
+    src = vp_yuv_frames(format=int(pixel_format), matrix=int(matrix), range=int(color_range))
+    for p, t in enumerate(planes):
+        want = chroma if p else (N, H, W)
+        if t.dtype not in words or tuple(t.shape) != want or t.device != y.device:
+            raise ValueError(f"plane {p} must be {words[0]} {want} on the Y plane's device, got {t.dtype} {tuple(t.shape)}")
+        inner = t.stride()[2:]
+        if any(s != w for s, w, n in zip(inner, (2, 1) if len(inner) == 2 else (1,), want[2:]) if n > 1):
+            raise ValueError(f"plane {p} must have contiguous samples" + (" (U,V pairs)" if len(inner) == 2 else ""))
+        item = t.element_size()
+        row_bytes = want[2] * (2 if len(inner) == 2 else 1) * item
+        # a dimension of extent 1 may carry any stride: give the packed one
+        row_stride = t.stride(1) * item if want[1] > 1 else row_bytes
+        src.plane[p] = t.data_ptr()
+        src.row_stride[p] = row_stride
+        src.frame_stride[p] = t.stride(0) * item if N > 1 else want[1] * row_stride
+    return src, N, H, W
+
+
+def op_preprocess_yuv(planes, pixel_format=VP_YUV_NV12, matrix=VP_YUV_BT601, color_range=VP_YUV_LIMITED,
+                      frame_idx=None, mode=VP_RESIZE_CENTER_CROP, size=288, out=None, stream=None):
+    """4:2:0 decoder planes (see yuv_frames; read in place) -> uint8 RGB [F, size, size, 3]: op_preprocess_frames
+    on the RGB frames the planes stand for, which are never stored."""
+    import torch
+    src, N, H, W = yuv_frames(planes, pixel_format, matrix, color_range)
+    y = planes[0]
+    if frame_idx is not None and (frame_idx.dtype != torch.int32 or frame_idx.dim() != 1 or
+                                  not frame_idx.is_contiguous() or frame_idx.device != y.device):
+        raise ValueError("frame_idx must be a contiguous int32 vector on the planes' device")
+    F = N if frame_idx is None else frame_idx.shape[0]
+    if out is None:
+        out = torch.empty((F, size, size, 3), dtype=torch.uint8, device=y.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (F, size, size, 3) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous uint8 {(F, size, size, 3)}")
+    with torch.cuda.device(y.device):  # the entry point has no handle: it launches on the current device
+        call("vp_op_preprocess_yuv", ctypes.byref(src), N, H, W, _ptr(frame_idx), F, int(mode), size, _ptr(out),
+             _stream(stream))
+    return out
