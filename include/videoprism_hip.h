@@ -466,6 +466,31 @@ int vp_op_topk(const float* queries, int64_t Q, const void* gallery, int gallery
 int vp_op_topk_merge(const float* scores_in, const int64_t* ids_in, int64_t parts, int64_t Q, int64_t k_in, int64_t k,
                      float* scores, int64_t* ids, void* stream);
 
+/* ---------------- grouped gallery search: the k best groups, each with its best row ----------------
+ * Several gallery rows may stand for one thing (the windows of a video, the views of a clip, the prompts of a class):
+ * labels[r] (device int64 [N], 8-byte aligned) names row r's group.  A group's score is the largest score of its rows
+ * and its best row is the row with that score, of equal scores the one with the smallest id.  The result lists the k
+ * best groups per query, score descending and equal scores by ascending id of the best row:
+ *   scores [Q, k] fp32, groups [Q, k] int64, ids [Q, k] int64 = id_base + best row; with fewer than k groups the tail
+ *   is (-inf, -1, -1).  A row that scores NaN or -inf, or whose label is negative, is never returned and never stands
+ *   for a group: a negative label blanks a row out.  Labels are arbitrary non-negative int64 (not dense, not sorted).
+ * The selection happens in the scan's lists (one entry per group), so the result is exact for every k <= 128 however
+ * many rows a group has.  Everything else is vp_op_topk's: the same scores bit for bit, the same limits on D, ld, k and
+ * the dtypes, stateless, asynchronous on `stream`, Q == 0 launches nothing, N == 0 gives all padding (labels may then
+ * be null).  The lists hold 16 B an entry, so a workgroup takes 32 queries only up to k = 63 at D = 1024.
+ *   ws       vp_op_topk_groups_workspace_bytes(Q, k) bytes (no device needed)
+ * vp_op_topk_groups_merge: the best k <= k_in (<= 128) groups per query of `parts` lists [parts, Q, k_in] as the search
+ * writes them (sorted, one entry per group, ids < 0 are padding).  Two lists may hold the same group (groups may span
+ * shards): of a group's entries the one that comes first in the order stays.  The result depends on the set of
+ * (score, group, id) alone, so shards searched with their id_base and label slices merge to the bits of the whole. */
+int vp_op_topk_groups_workspace_bytes(int64_t Q, int64_t k, size_t* bytes);
+int vp_op_topk_groups(const float* queries, int64_t Q, const void* gallery, int gallery_dtype, int64_t N, int64_t ld,
+                      int64_t D, const int64_t* labels, int64_t k, int64_t id_base, float* scores, int64_t* groups,
+                      int64_t* ids, void* ws, size_t ws_bytes, void* stream);
+int vp_op_topk_groups_merge(const float* scores_in, const int64_t* groups_in, const int64_t* ids_in, int64_t parts,
+                            int64_t Q, int64_t k_in, int64_t k, float* scores, int64_t* groups, int64_t* ids,
+                            void* stream);
+
 /* ---------------- multi-GPU: RCCL all-gather of pooled clip embeddings ----------------
  * The reference runs on one device; its video-text usage scores every clip against every query,
  * `similarities = video_emb @ text_emb.T` (README.md:81, verify_clip_models.py:84).  With clips

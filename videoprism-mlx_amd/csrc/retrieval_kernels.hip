@@ -30,6 +30,16 @@
 // plus the number of the other list's elements that come before it (binary search; on a full tie the even list first),
 // so every output slot is written by exactly one thread.  The order (score descending, id ascending, padding last) is
 // total, which makes the result independent of how the rows were split into lists.
+//
+// The grouped search (vp_op_topk_groups*; DESIGN.md §4 "Grouped gallery search") is topk_scan_kernel<BF16, true>, the
+// same text with a label per list entry, and topk_groups_merge_kernel.  Scores, tiling, the pre-check against the k-th
+// score and the waves' turns are shared; only the insert differs: a lane that beats the k-th score reads its row's
+// label (a negative one is skipped) and looks for it in the list during the walk that finds the worst entry.  A group
+// that is there with a score not smaller stays as it is, one with a smaller score is overwritten in place, and
+// otherwise the worst entry goes, as above.  The k-th score only rises and a group leaves a list only when k others
+// beat it, so the list is the best k groups of the rows seen, each with its best row (of equal scores the first).
+// The labels of a lane's candidates in a tile are read together, and of candidates that follow one another in a lane
+// with the same label only the best keeps its turn (tk_insert).
 #include "vp_common.h"
 #include "vp_kernels.h"
 
@@ -98,29 +108,105 @@ __device__ __forceinline__ void tk_mma(const f32x4 (&a)[2][4], const f32x4* bq, 
   }
 }
 
-// The wave's rows that beat their query's k-th score enter its list, in row order (see the file comment).
+// The wave's rows that beat their query's k-th score enter its list, in row order (see the file comment).  GROUPED: the
+// list holds one entry per group (llb: the entries' labels; labels: the rows' labels in memory).
+template <bool GROUPED>
 __device__ __forceinline__ void tk_insert(const f32x16 (&acc)[2], int64_t r0, int64_t p0, int64_t p1, int k, int i,
-                                          int half, bool qlane, float* lsc, uint32_t* lid) {
+                                          int half, bool qlane, float* lsc, uint32_t* lid, int64_t* llb,
+                                          const int64_t* __restrict__ labels) {
   float* sc = lsc + i * k;
   uint32_t* id = lid + i * k;
   __threadfence_block();
   float thr = qlane ? sc[k - 1] : INFINITY;
 #pragma unroll
   for (int rt = 0; rt < 2; ++rt) {
+    // GROUPED: the labels of the lane's rows of this tile that beat the k-th score, read together before the rows take
+    // their turns (one latency a tile, not one a candidate; the k-th score only rises, so no later candidate is missed)
+    int64_t lab[GROUPED ? 16 : 1];
+    if constexpr (GROUPED) {
+      bool c16 = false;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) {
+        const int64_t row = r0 + 32 * rt + (q & 3) + 8 * (q >> 2) + 4 * half;
+        const bool ok = row < p1 && acc[rt][q] > thr;
+        c16 |= ok;
+        lab[q] = ok ? labels[row] : (int64_t)-1;
+      }
+      if (__ballot(c16) == 0) continue;
+      // Of the lane's candidates that follow one another with the same label only the best can be its group's best row
+      // (of equal scores the first), so the others give up their turn: forwards a row that an earlier one of its run
+      // equals or beats, backwards a row that a later one beats.  With a video's windows in neighbouring rows this
+      // leaves one candidate a lane instead of 16; what the lists end up holding does not depend on it.
+      {
+        int64_t cl = -1;
+        float cs = 0.f;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          if (lab[q] < 0) continue;
+          if (lab[q] != cl) cl = lab[q], cs = acc[rt][q];
+          else if (acc[rt][q] > cs) cs = acc[rt][q];
+          else lab[q] = -1;
+        }
+        cl = -1;
+#pragma unroll
+        for (int q = 15; q >= 0; --q) {
+          if (lab[q] < 0) continue;
+          if (lab[q] != cl) cl = lab[q], cs = acc[rt][q];
+          else if (acc[rt][q] >= cs) cs = acc[rt][q];
+          else lab[q] = -1;
+        }
+      }
+    }
+    auto live = [&](int q) {  // GROUPED: the candidate kept its turn (and its label is not negative)
+      if constexpr (GROUPED) return lab[q] >= 0;
+      else return true;
+    };
 #pragma unroll
     for (int qb = 0; qb < 4; ++qb) {  // rows 8 qb .. 8 qb + 7 of the tile: acc[4 qb .. 4 qb + 3] of both halves
       bool c4 = false;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) c4 |= r0 + 32 * rt + 8 * qb + 4 * half + e < p1 && acc[rt][4 * qb + e] > thr;
+      for (int e = 0; e < 4; ++e)
+        c4 |= r0 + 32 * rt + 8 * qb + 4 * half + e < p1 && acc[rt][4 * qb + e] > thr && live(4 * qb + e);
       if (__ballot(c4) == 0) continue;
 #pragma unroll
       for (int jj = 8 * qb; jj < 8 * qb + 8; ++jj) {
         const int q = (jj & 3) + 4 * (jj >> 3);  // row jj is acc[q] of the lanes with half == (jj >> 2) & 1
         const int64_t row = r0 + 32 * rt + jj;
         const float v = acc[rt][q];
-        const bool c = half == ((jj >> 2) & 1) && row < p1 && v > thr;
+        const bool c = half == ((jj >> 2) & 1) && row < p1 && v > thr && live(q);
         if (__ballot(c) != 0) {
-          if (c) {
+          if constexpr (GROUPED) {
+            // the same walk also looks for the row's group in slots 0 .. k - 2.  Found there with a score not smaller:
+            // nothing changes (rows ascend, so an equal score has the smaller row already).  Found with a smaller
+            // score: overwritten in place, and slot k - 1 is still the worst.  Not found, or found in slot k - 1 (whose
+            // score v beats): the new entry takes slot k - 1 and trades places with the worst, as in the ungrouped path
+            const int64_t g = lab[q];
+            if (c) {
+              int64_t* lb = llb + i * k;
+              const uint32_t rr = (uint32_t)(row - p0);
+              float ws = v;
+              uint32_t wr = rr;
+              int64_t wl = g;
+              int wp = k - 1, mp = -1;
+              for (int p = 0; p < k - 1; ++p) {
+                const float s = sc[p];
+                const uint32_t r = id[p];
+                const int64_t l = lb[p];
+                if (l == g) mp = p;
+                if (s < ws || (s == ws && r > wr)) ws = s, wr = r, wl = l, wp = p;
+              }
+              if (mp >= 0) {
+                if (sc[mp] < v) sc[mp] = v, id[mp] = rr;
+              } else {
+                sc[wp] = v;
+                id[wp] = rr;
+                lb[wp] = g;
+                sc[k - 1] = ws;
+                id[k - 1] = wr;
+                lb[k - 1] = wl;
+              }
+            }
+          } else if (c) {
             // the new entry evicts slot k - 1, the worst; the worst of the k now there (lowest score, of equal scores
             // the largest row) trades places with it
             const uint32_t rr = (uint32_t)(row - p0);
@@ -145,16 +231,20 @@ __device__ __forceinline__ void tk_insert(const f32x16 (&acc)[2], int64_t r0, in
   }
 }
 
-template <bool BF16>
+template <bool BF16, bool GROUPED>
 __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __restrict__ queries, int64_t Q,
                                                         const void* __restrict__ gallery, int64_t N, int64_t ld, int D,
                                                         int k, int G, int64_t rows_per_part, int64_t id_base,
-                                                        float* __restrict__ ws_sc, int64_t* __restrict__ ws_id) {
+                                                        float* __restrict__ ws_sc, int64_t* __restrict__ ws_id,
+                                                        const int64_t* __restrict__ labels,
+                                                        int64_t* __restrict__ ws_gr) {
   extern __shared__ __attribute__((aligned(16))) char tk_smem[];
   f32x4* bq = reinterpret_cast<f32x4*>(tk_smem);                          // D * G * 4 bytes, fragment order
   float* lsc = reinterpret_cast<float*>(tk_smem + (size_t)D * G * 4);     // [G][k]
   uint32_t* lid = reinterpret_cast<uint32_t*>(lsc + G * k);               // [G][k] row - p0
   volatile int* flags = reinterpret_cast<volatile int*>(lid + G * k);     // [2][kTkWaves]
+  // GROUPED: [G][k] labels behind the flags (a multiple of 8 bytes from the start)
+  int64_t* llb = GROUPED ? reinterpret_cast<int64_t*>(const_cast<int*>(flags) + 2 * kTkWaves) : nullptr;
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6, i = lane & 31, half = lane >> 5;
   const int64_t q0 = (int64_t)blockIdx.y * G;
@@ -162,6 +252,7 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
   for (int e = tid; e < G * k; e += kTkThreads) {
     lsc[e] = -INFINITY;
     lid[e] = kTkNoRow;
+    if constexpr (GROUPED) llb[e] = -1;  // matches no row's label: a lane skips a negative one
   }
   if constexpr (BF16) {
     const int nc = D >> 3;  // chunks of 8 values: step c >> 1, half c & 1
@@ -236,7 +327,7 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
 #pragma unroll
     for (int ww = 0; ww < kTkWaves; ++ww) {
       if (flags[par * kTkWaves + ww]) {  // the same for every thread
-        if (w == ww) tk_insert(acc, r0, p0, p1, k, i, half, qlane, lsc, lid);
+        if (w == ww) tk_insert<GROUPED>(acc, r0, p0, p1, k, i, half, qlane, lsc, lid, llb, labels);
         __syncthreads();
       }
     }
@@ -259,6 +350,7 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
     const int64_t o = (part * Q + q0 + qi) * k + rank;
     ws_sc[o] = s;
     ws_id[o] = r == kTkNoRow ? (int64_t)-1 : id_base + p0 + (int64_t)r;
+    if constexpr (GROUPED) ws_gr[o] = llb[e];  // -1 where the slot was never filled
   }
 }
 
@@ -334,16 +426,130 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const float* __restrict
   }
 }
 
+// The grouped merge: topk_merge_kernel's rounds and pairwise tree over lists of (score, group, id), one entry per group.
+// At a pairwise step an entry is dropped when the other list holds its group with an entry that comes before it (of
+// two identical entries the odd list's goes); a survivor's place is the number of survivors before it in its own list
+// plus the number of the other list's survivors that come before it.  The dropped entries leave holes, so both numbers
+// are counted, not searched; the output list is cleared first and every survivor writes its own slot.
+__global__ __launch_bounds__(256) void topk_groups_merge_kernel(const float* __restrict__ sin,
+                                                                const int64_t* __restrict__ gin,
+                                                                const int64_t* __restrict__ iin, int64_t parts,
+                                                                int64_t Q, int k_in, int k, int L,
+                                                                float* __restrict__ so, int64_t* __restrict__ go,
+                                                                int64_t* __restrict__ io) {
+  extern __shared__ __attribute__((aligned(16))) char mg_smem[];
+  // two buffers of L lists of k_in entries, and one flag per entry of a buffer
+  int64_t* idb = reinterpret_cast<int64_t*>(mg_smem);
+  int64_t* grb = idb + 2 * L * k_in;
+  float* scb = reinterpret_cast<float*>(grb + 2 * L * k_in);
+  int* live = reinterpret_cast<int*>(scb + 2 * L * k_in);
+  const int tid = threadIdx.x;
+  const int64_t q = blockIdx.x;
+  const int LK = L * k_in;
+  int cur = 0;
+  for (int e = tid; e < k_in; e += 256) {  // list 0: the running result
+    scb[e] = -INFINITY;
+    idb[e] = -1;
+    grb[e] = -1;
+  }
+  for (int64_t base = 0; base < parts; base += L - 1) {
+    for (int e = tid; e < LK - k_in; e += 256) {
+      const int64_t p = base + e / k_in;
+      float s = -INFINITY;
+      int64_t id = -1, g = -1;
+      if (p < parts) {
+        const int64_t o = (p * Q + q) * k_in + e % k_in;
+        s = sin[o];
+        id = iin[o];
+        g = gin[o];
+        if (!(s > -INFINITY) || id < 0 || g < 0) s = -INFINITY, id = -1, g = -1;  // NaN, -inf and blanks never rank
+      }
+      scb[cur * LK + k_in + e] = s;
+      idb[cur * LK + k_in + e] = id;
+      grb[cur * LK + k_in + e] = g;
+    }
+    __syncthreads();
+    for (int n = L; n > 1; n >>= 1) {
+      const float* cs = scb + cur * LK;
+      const int64_t* ci = idb + cur * LK;
+      const int64_t* cg = grb + cur * LK;
+      float* ns = scb + (cur ^ 1) * LK;
+      int64_t* ni = idb + (cur ^ 1) * LK;
+      int64_t* ng = grb + (cur ^ 1) * LK;
+      for (int e = tid; e < n * k_in; e += 256) {
+        const int l = e / k_in;
+        const float s = cs[e];
+        const int64_t id = ci[e], g = cg[e];
+        bool alive = id >= 0;
+        if (alive) {
+          const int ob = (l ^ 1) * k_in;
+          for (int p = 0; p < k_in; ++p) {
+            if (cg[ob + p] != g) continue;
+            const float s2 = cs[ob + p];
+            const int64_t i2 = ci[ob + p];
+            if (tk_beats(s2, i2, s, id) || ((l & 1) && s2 == s && i2 == id)) alive = false;
+          }
+        }
+        live[e] = alive;
+        if (e < (n >> 1) * k_in) {
+          ns[e] = -INFINITY;
+          ni[e] = -1;
+          ng[e] = -1;
+        }
+      }
+      __syncthreads();
+      for (int e = tid; e < n * k_in; e += 256) {
+        if (!live[e]) continue;
+        const int l = e / k_in, j = e % k_in;
+        const float s = cs[e];
+        const int64_t id = ci[e];
+        int rank = 0;
+        for (int p = 0; p < j; ++p) rank += live[l * k_in + p];
+        const int ob = (l ^ 1) * k_in;
+        for (int p = 0; p < k_in; ++p) {
+          const float s2 = cs[ob + p];
+          const int64_t i2 = ci[ob + p];
+          const bool before = (l & 1) ? !tk_beats(s, id, s2, i2) : tk_beats(s2, i2, s, id);
+          rank += live[ob + p] && before;
+        }
+        if (rank < k_in) {
+          ns[(l >> 1) * k_in + rank] = s;
+          ni[(l >> 1) * k_in + rank] = id;
+          ng[(l >> 1) * k_in + rank] = cg[e];
+        }
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < k; e += 256) {
+    so[q * k + e] = scb[cur * LK + e];
+    io[q * k + e] = idb[cur * LK + e];
+    go[q * k + e] = grb[cur * LK + e];
+  }
+}
+
 }  // namespace
 
 int topk_group(int D, int k) {
   return D <= 1024 && (size_t)D * 32 * 4 + (size_t)32 * k * 8 + 64 <= (size_t)kTkLdsBytes ? 32 : 16;
 }
 
-hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D, int k,
-                     int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s) {
+// the grouped lists hold an int64 label per entry: 16 B instead of 8
+int topk_groups_group(int D, int k) {
+  return D <= 1024 && (size_t)D * 32 * 4 + (size_t)32 * k * 16 + 64 <= (size_t)kTkLdsBytes ? 32 : 16;
+}
+
+namespace {
+
+// both searches: labels == nullptr is the ungrouped one (ws_gr unused)
+template <bool GROUPED>
+hipError_t topk_scan_launch(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
+                            int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id, int64_t* ws_gr,
+                            int* parts_out, hipStream_t s) {
   if (Q < 1 || N < 0 || D < 64 || D % 64 || D > kPoolMaxD || k < 1 || k > kTopkMaxK || ld < D) return hipErrorInvalidValue;
-  const int G = topk_group(D, k);
+  const int G = GROUPED ? topk_groups_group(D, k) : topk_group(D, k);
   const int64_t groups = (Q + G - 1) / G;
   if (groups > 65535) return hipErrorInvalidValue;
   // about one workgroup per CU (each takes most of a CU's LDS), every range a whole number of tiles
@@ -354,20 +560,36 @@ hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int b
   const int64_t rows_per_part = tiles < 1 ? kTkRows : (tiles + parts - 1) / parts * kTkRows;
   if (rows_per_part >= (int64_t)kTkNoRow) return hipErrorInvalidValue;
   parts = tiles < 1 ? 1 : (N + rows_per_part - 1) / rows_per_part;
-  const int lds = D * G * 4 + G * k * 8 + 2 * kTkWaves * 4;
-  const void* fn = bf16 ? reinterpret_cast<const void*>(&topk_scan_kernel<true>)
-                        : reinterpret_cast<const void*>(&topk_scan_kernel<false>);
+  const int lds = D * G * 4 + G * k * (GROUPED ? 16 : 8) + 2 * kTkWaves * 4;
+  const void* fn = bf16 ? reinterpret_cast<const void*>(&topk_scan_kernel<true, GROUPED>)
+                        : reinterpret_cast<const void*>(&topk_scan_kernel<false, GROUPED>);
   hipError_t e = ensure_dyn_lds(fn, kTkLdsBytes);
   if (e != hipSuccess) return e;
   const dim3 grid((unsigned)parts, (unsigned)groups);
   if (bf16)
-    hipLaunchKernelGGL(topk_scan_kernel<true>, grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N, ld, D, k, G,
-                       rows_per_part, id_base, ws_sc, ws_id);
+    hipLaunchKernelGGL((topk_scan_kernel<true, GROUPED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N, ld, D,
+                       k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr);
   else
-    hipLaunchKernelGGL(topk_scan_kernel<false>, grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N, ld, D, k, G,
-                       rows_per_part, id_base, ws_sc, ws_id);
+    hipLaunchKernelGGL((topk_scan_kernel<false, GROUPED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N, ld, D,
+                       k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr);
   *parts_out = (int)parts;
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D, int k,
+                     int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s) {
+  return topk_scan_launch<false>(queries, Q, gallery, bf16, N, ld, D, k, nullptr, id_base, ws_sc, ws_id, nullptr,
+                                 parts_out, s);
+}
+
+hipError_t topk_groups_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
+                            int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id, int64_t* ws_gr,
+                            int* parts_out, hipStream_t s) {
+  if (!labels && N > 0) return hipErrorInvalidValue;
+  return topk_scan_launch<true>(queries, Q, gallery, bf16, N, ld, D, k, labels, id_base, ws_sc, ws_id, ws_gr, parts_out,
+                                s);
 }
 
 hipError_t topk_merge(const float* sin, const int64_t* iin, int64_t parts, int64_t Q, int k_in, int k, float* so,
@@ -379,6 +601,19 @@ hipError_t topk_merge(const float* sin, const int64_t* iin, int64_t parts, int64
   while (L < 256 && L < parts + 1 && (size_t)2 * (2 * L) * k_in * 12 <= 48 * 1024) L *= 2;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)Q), dim3(256), (size_t)2 * L * k_in * 12, s, sin, iin, parts, Q,
                      k_in, k, L, so, io);
+  return hipGetLastError();
+}
+
+hipError_t topk_groups_merge(const float* sin, const int64_t* gin, const int64_t* iin, int64_t parts, int64_t Q, int k_in,
+                             int k, float* so, int64_t* go, int64_t* io, hipStream_t s) {
+  if (parts < 1 || Q < 1 || Q > 0x7fffffff || k_in < 1 || k_in > kTopkMaxK || k < 1 || k > k_in)
+    return hipErrorInvalidValue;
+  // an entry takes 20 B in each of the two buffers and a 4 B flag: as many lists at a time as 48 KB hold (8 at
+  // k_in = 128), no more than there are
+  int L = 2;
+  while (L < 256 && L < parts + 1 && (size_t)(2 * L) * k_in * 44 <= 48 * 1024) L *= 2;
+  hipLaunchKernelGGL(topk_groups_merge_kernel, dim3((unsigned)Q), dim3(256), (size_t)L * k_in * 44, s, sin, gin, iin,
+                     parts, Q, k_in, k, L, so, go, io);
   return hipGetLastError();
 }
 

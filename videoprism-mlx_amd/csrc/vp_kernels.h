@@ -284,6 +284,18 @@ hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int b
 // pass 2: the best k <= k_in of `parts` such lists [parts][Q][k_in] per query, same order, ties between lists by id
 hipError_t topk_merge(const float* sin, const int64_t* iin, int64_t parts, int64_t Q, int k_in, int k, float* so,
                       int64_t* io, hipStream_t s);
+// the grouped search (DESIGN.md §4 "Grouped gallery search"): row r belongs to group labels[r] (int64; negative = the
+// row is blanked out), a group scores as its best row, and the lists hold one entry per group: (score, id of the best
+// row, group).  Same passes and the same scores as above; the lists carry an int64 label per entry in LDS, so the
+// queries of a workgroup are chosen against 16 B an entry
+int topk_groups_group(int D, int k);
+hipError_t topk_groups_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
+                            int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id, int64_t* ws_gr,
+                            int* parts_out, hipStream_t s);
+// the merge drops an entry when another list holds its group with an entry that comes before it, so the result is a
+// function of the set of (score, group, id) alone
+hipError_t topk_groups_merge(const float* sin, const int64_t* gin, const int64_t* iin, int64_t parts, int64_t Q, int k_in,
+                             int k, float* so, int64_t* go, int64_t* io, hipStream_t s);
 
 // ---- frame ingest (preprocess.hip) ----
 // video_utils.py:109-124: size of the resized frame and the crop window's origin in it (mode 0 centre

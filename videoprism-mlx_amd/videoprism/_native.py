@@ -217,8 +217,15 @@ _SIGNATURES = {
                            c_void_p, c_void_p, c_size_t, c_void_p]),
     "vp_op_topk_merge": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                  c_void_p]),
+    # grouped gallery search: the k best groups of rows, each with its best row (EmbeddingIndex.search_groups)
+    "vp_op_topk_groups_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
+    "vp_op_topk_groups": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64,
+                                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_op_topk_groups_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
     # not in the public header: queries per workgroup of the search at (D, k) (tools/retrieval_bench.py); no GPU call
     "vp_dev_topk_group": (c_int, [c_int64, c_int64]),
+    "vp_dev_topk_groups_group": (c_int, [c_int64, c_int64]),
     # not in the public header: one streaming pass of the backward on its own (tools/probe_bench.py)
     "vp_dev_probe_backward_pass": (c_int, [POINTER(vp_probe_dims), c_void_p, c_int, c_int64, c_int64, c_int, c_void_p,
                                            c_size_t, c_void_p]),
@@ -704,6 +711,56 @@ def op_topk_merge(scores, ids, k, stream=None):
         call("vp_op_topk_merge", _ptr(scores), _ptr(ids), parts, Q, k_in, k, _ptr(out_s), _ptr(out_i),
              _stream(stream))
     return out_s, out_i
+
+
+def op_topk_groups_workspace_bytes(Q, k) -> int:
+    n = c_size_t()
+    call("vp_op_topk_groups_workspace_bytes", Q, k, ctypes.byref(n))
+    return n.value
+
+
+def op_topk_groups(queries, gallery, labels, k, id_base=0, stream=None, ws=None):
+    """The k best groups of gallery rows per row of queries [Q, D] (fp32): labels [N] int64 names each row's group (a
+    negative label blanks the row out), a group scores as its best row, and the result is (scores [Q, k] fp32,
+    groups [Q, k] int64, ids [Q, k] int64 = id_base + best row), score descending and equal scores by ascending id;
+    fewer than k groups leave (-inf, -1, -1).  Gallery and `ws` as op_topk (op_topk_groups_workspace_bytes)."""
+    import torch
+    Q, D = queries.shape
+    N = gallery.shape[0]
+    if gallery.dim() != 2 or gallery.shape[1] != D or (N > 1 and gallery.stride(1) != 1):
+        raise ValueError(f"gallery must be [N, {D}] with contiguous rows, got {tuple(gallery.shape)}")
+    if queries.dtype != torch.float32:
+        raise TypeError("queries must be fp32")
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (N,):
+        raise ValueError(f"labels must be int64 [{N}], got {labels.dtype} {tuple(labels.shape)}")
+    queries, labels = queries.contiguous(), labels.contiguous()
+    ld = gallery.stride(0) if N > 1 else D
+    scores = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    groups = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    if Q == 0:
+        return scores, groups, ids
+    if ws is None:
+        ws = torch.empty(op_topk_groups_workspace_bytes(Q, k), dtype=torch.uint8, device=queries.device)
+    with torch.cuda.device(queries.device):  # no handle: the op launches on the current device
+        call("vp_op_topk_groups", _ptr(queries), Q, _ptr(gallery), _prec(gallery), N, ld, D, _ptr(labels), k, id_base,
+             _ptr(scores), _ptr(groups), _ptr(ids), _ptr(ws), ws.numel(), _stream(stream))
+    return scores, groups, ids
+
+
+def op_topk_groups_merge(scores, groups, ids, k, stream=None):
+    """The best k groups per query of lists scores / groups / ids [parts, Q, k_in] as op_topk_groups returns them; of a
+    group's entries in several lists the one that comes first in the order stays."""
+    import torch
+    parts, Q, k_in = scores.shape
+    scores, groups, ids = scores.contiguous(), groups.contiguous(), ids.contiguous()
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=scores.device)
+    out_g = torch.empty((Q, k), dtype=torch.int64, device=scores.device)
+    out_i = torch.empty((Q, k), dtype=torch.int64, device=scores.device)
+    with torch.cuda.device(scores.device):
+        call("vp_op_topk_groups_merge", _ptr(scores), _ptr(groups), _ptr(ids), parts, Q, k_in, k, _ptr(out_s),
+             _ptr(out_g), _ptr(out_i), _stream(stream))
+    return out_s, out_g, out_i
 
 
 def op_layernorm(x, gamma1p, beta, out_dtype=None, perm=PERM_NONE, T=1, Nsp=1, add=None,

@@ -43,6 +43,7 @@ class EmbeddingIndex:
         self.dtype = dtype
         self.device = torch.device(device)
         self._buf = torch.empty((max(int(capacity), 0), self.dim), dtype=dtype, device=self.device)
+        self._labels = None  # int64 [capacity] once rows are added with `group`
         self._len = 0
 
     def __len__(self) -> int:
@@ -57,9 +58,18 @@ class EmbeddingIndex:
         """The stored [len, dim] rows (a view of the buffer)."""
         return self._buf[:self._len]
 
-    def add(self, emb) -> range:
+    @property
+    def groups(self):
+        """The stored rows' labels, int64 [len] (a view of the label buffer); None on an index without labels."""
+        return None if self._labels is None else self._labels[:self._len]
+
+    def add(self, emb, group=None) -> range:
         """Appends emb [n, dim] (NumPy or torch, fp32 or bf16), rounded to the storage dtype once; returns the new
-        rows' ids, range(len_before, len_after).  The buffer grows by doubling."""
+        rows' ids, range(len_before, len_after).  The buffer grows by doubling.
+
+        `group` labels the new rows for `search_groups`: an int (every new row belongs to that one group, for example
+        all windows of one video) or an int64 array [n]; a negative label blanks a row out of the grouped search.  An
+        index holds labels for all of its rows or for none: mixing the two kinds of `add` raises ValueError."""
         import torch
         emb, _ = _as_tensor(emb, self.device)
         if emb.dim() != 2 or emb.shape[1] != self.dim:
@@ -67,6 +77,18 @@ class EmbeddingIndex:
         if emb.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError(f"emb must be fp32 or bf16, got {emb.dtype}")
         n = int(emb.shape[0])
+        if group is None and self._labels is not None:
+            raise ValueError("this index holds group labels: add(emb, group=...) is required")
+        if group is not None and self._labels is None and self._len > 0:
+            raise ValueError("this index holds rows without group labels: add(emb) without group is required")
+        labels = None
+        if group is not None:
+            if isinstance(group, (int, np.integer)):
+                labels = torch.full((n,), int(group), dtype=torch.int64, device=self.device)
+            else:
+                labels, _ = _as_tensor(group, self.device)
+                if labels.dtype != torch.int64 or tuple(labels.shape) != (n,):
+                    raise ValueError(f"group must be an int or int64 [{n}], got {labels.dtype} {tuple(labels.shape)}")
         need = self._len + n
         if need > self.capacity:
             cap = max(self.capacity, 1)
@@ -75,6 +97,13 @@ class EmbeddingIndex:
             buf = torch.empty((cap, self.dim), dtype=self.dtype, device=self.device)
             buf[:self._len].copy_(self._buf[:self._len])
             self._buf = buf
+        if labels is not None:
+            if self._labels is None or self._labels.shape[0] < self.capacity:  # grows with the rows
+                lab = torch.empty((self.capacity,), dtype=torch.int64, device=self.device)
+                if self._labels is not None:
+                    lab[:self._len].copy_(self._labels[:self._len])
+                self._labels = lab
+            self._labels[self._len:need].copy_(labels)
         self._buf[self._len:need].copy_(emb)
         ids = range(self._len, need)
         self._len = need
@@ -105,3 +134,35 @@ class EmbeddingIndex:
         if from_numpy:
             return scores.cpu().numpy(), ids.cpu().numpy()
         return scores, ids
+
+    def search_groups(self, queries, k: int, comm=None, id_base: int = 0):
+        """(scores [Q, k] fp32, groups [Q, k] int64, ids [Q, k] int64) of queries [Q, dim]: each query's k best groups
+        of rows (`add(emb, group=...)`), a group scoring as its best row, with that row's id (id_base + row; of equal
+        scores the smallest).  Score descending, equal scores by ascending id; with fewer than k groups the tail is
+        (-inf, -1, -1); rows with a negative label, a NaN or a -inf score never count.  Exact for every k up to 128
+        however many rows a group holds: the selection happens in the search kernel's lists (`vp_op_topk_groups`).
+        For a gallery of sliding windows, `groups` are the videos and `ids` minus a video's first id is the window.
+        NumPy in gives NumPy out, tensors in give tensors out; ValueError on an index without labels.
+
+        With `comm` every rank holds a shard (groups may span shards): the three lists are gathered as `search`
+        gathers its two and merged on every rank, to the bits of the whole gallery's search."""
+        import torch
+        if self._labels is None:
+            raise ValueError("search_groups needs group labels: add(emb, group=...)")
+        q, from_numpy = _as_tensor(queries, self.device)
+        if q.dim() != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
+        q = q.float().contiguous()
+        k = int(k)
+        scores, groups, ids = _native.op_topk_groups(q, self.embeddings, self.groups, k, id_base=int(id_base))
+        if comm is not None and q.shape[0] > 0:
+            Q = int(q.shape[0])
+            counts = [Q] * comm.world
+            all_s = comm.all_gather_rows(scores, counts=counts)
+            all_g = comm.all_gather_rows(groups.view(torch.uint8), counts=counts).view(torch.int64)
+            all_i = comm.all_gather_rows(ids.view(torch.uint8), counts=counts).view(torch.int64)
+            scores, groups, ids = _native.op_topk_groups_merge(
+                all_s.view(comm.world, Q, k), all_g.view(comm.world, Q, k), all_i.view(comm.world, Q, k), k)
+        if from_numpy:
+            return scores.cpu().numpy(), groups.cpu().numpy(), ids.cpu().numpy()
+        return scores, groups, ids
