@@ -3,6 +3,7 @@
 device buffers, timed in interleaved rounds, and their outputs compared bitwise.
 
   python tools/ab_lib.py tattn .ab/old/videoprism-mlx_amd/videoprism/libvideoprism_hip.so
+  python tools/ab_lib.py gemm old=.ab/old/videoprism-mlx_amd/videoprism/libvideoprism_hip.so [NAME=LIB.so ...]
 """
 import ctypes
 import os
@@ -248,6 +249,85 @@ def pooler(other, control=False):
         ab(f"probe forward {shape}", fwd, out)
 
 
+def gemm(others, rounds=7):
+    """The forward's 4-wave GEMM launches at the bench shapes (Base, B = 32: M = 131072) on random operands:
+    ffn_layer1 (EPI 16, no padded rows), ffn_layer2 (17), the spatial q|k|v (19), post (10), the two fused
+    temporal launches (14, 15) and the patch embedding from 512 frames.  `others`: NAME=LIB.so ...; every
+    library is loaded beside this tree's, fed the same buffers, compared bitwise with this tree's output and
+    timed in interleaved rounds (median and min per arm)."""
+    import statistics
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    libs = {"this": nat.load()}
+    for spec in others:
+        name, path = spec.split("=", 1)
+        libs[name] = ctypes.CDLL(path)
+    names = ("vp_dev_gemm_ln", "vp_dev_gemm_tattn", "vp_dev_patch_embed")
+    for lib in libs.values():
+        for n in names:
+            f = getattr(lib, n)
+            f.restype, f.argtypes = nat._SIGNATURES[n]
+    st = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    M, D, F, H = 131072, 768, 3072, 12
+
+    def ab(label, run, outs, flop):
+        for k in libs:
+            run(k)
+        torch.cuda.synchronize()
+        same = {k: all(torch.equal(a, b) for a, b in zip(outs["this"], outs[k])) for k in libs if k != "this"}
+        res = {k: [] for k in libs}
+        for _ in range(rounds):
+            for k in libs:
+                res[k].append(timeit(lambda k=k: run(k)))
+        wins = {k: sum(a < b for a, b in zip(res["this"], res[k])) for k in libs if k != "this"}
+        print(f"{label}: bitwise this == " + " ".join(f"{k}:{v}" for k, v in same.items()) + " | " + " | ".join(
+            f"{k} median {statistics.median(v)*1e3:7.1f} min {min(v)*1e3:7.1f} us ({flop/min(v)/1e9:6.1f} TF)"
+            for k, v in res.items()) + " | rounds this faster: " + " ".join(f"{k} {v}/{rounds}" for k, v in wins.items()),
+              flush=True)
+
+    rs = torch.stack([torch.rand(M, generator=g, device=dev) + 0.5, torch.randn(M, generator=g, device=dev) * 0.1],
+                     1).contiguous()
+    x = (torch.rand((M, D), generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
+    for label, N, K, epi in (("ffn1 <16,nopad,S2>", F, D, 16), ("ffn2 <17,S3>", D, F, 17), ("qkv <19,S3>", 3 * D, D, 19),
+                             ("post <10,S3>", D, D, 10)):
+        a = x if K == D else (torch.rand((M, K), generator=g, device=dev) * 2 - 1).to(torch.bfloat16)
+        w = ((torch.rand((N, K), generator=g, device=dev) * 2 - 1) / K ** 0.5).to(torch.bfloat16)
+        b = torch.randn(N, generator=g, device=dev) * 0.1
+        c = torch.randn(N, generator=g, device=dev) * 0.1
+        resid = epi in (17, 10)
+        r0 = torch.randn((M, N), generator=g, device=dev).to(torch.bfloat16) if resid else None
+        outs = {k: [torch.empty((M, N), device=dev, dtype=torch.bfloat16)] +
+                ([torch.empty((N // 128, M, 2), device=dev)] if resid else []) for k in libs}
+
+        def run(k, a=a, w=w, b=b, c=c, r0=r0, N=N, K=K, epi=epi, outs=outs, resid=resid):
+            _ok(libs[k].vp_dev_gemm_ln(epi, ptr(a), ptr(w), M, N, K, ptr(outs[k][0]), ptr(b), ptr(r0), None, 0, None,
+                                       ptr(rs), ptr(c), ptr(outs[k][1]) if resid else None, st()))
+        ab(label, run, outs, 2.0 * M * N * K)
+        del a, w, outs, r0
+
+    w = ((torch.rand((3 * D, D), generator=g, device=dev) * 2 - 1) / D ** 0.5).to(torch.bfloat16)
+    wqk, wv = w[:2 * D].contiguous(), w[2 * D:].contiguous()
+    b = torch.randn(3 * D, generator=g, device=dev) * 0.1
+    c = torch.randn(3 * D, generator=g, device=dev) * 0.1
+    p = {k: [torch.empty(M // 16 * H * 256, device=dev, dtype=torch.bfloat16)] for k in libs}
+    o = {k: [torch.empty(M, D, device=dev, dtype=torch.bfloat16)] for k in libs}
+    ab("tattn qk <14,S3>", lambda k: _ok(libs[k].vp_dev_gemm_tattn(0, ptr(x), ptr(wqk), M, D, ptr(p[k][0]), ptr(b), ptr(rs),
+                                                                   ptr(c), None, H, 50.0, st())), p, 2.0 * M * 2 * D * D)
+    ab("tattn v <15,S3>", lambda k: _ok(libs[k].vp_dev_gemm_tattn(1, ptr(x), ptr(wv), M, D, ptr(o[k][0]), ptr(b[2 * D:]),
+                                                                  ptr(rs), ptr(c[2 * D:]), ptr(p["this"][0]), H, 50.0,
+                                                                  st())), o, 2.0 * M * D * D)
+    del p, o
+    P, frames = 18, M // 256
+    v = (torch.rand((frames, 16 * P, 16 * P, 3), generator=g, device=dev) * 4 - 1).to(torch.bfloat16)
+    kb = (torch.randn((P * P * 3, D), generator=g, device=dev) / (P * P * 3) ** 0.5).to(torch.bfloat16)
+    wvid = nat.video_patch_w(kb.cpu(), P).to(dev)
+    pos = torch.randn((256, D), generator=g, device=dev) * 0.1
+    e = {k: [torch.empty(M, D, device=dev, dtype=torch.bfloat16)] for k in libs}
+    ab("patch embed <6,AVID>", lambda k: _ok(libs[k].vp_dev_patch_embed(ptr(v), frames, P, ptr(wvid), D, ptr(b), ptr(pos),
+                                                                       ptr(e[k][0]), st())), e, 2.0 * M * D * 64 * P)
+
+
 def _ok(rc):
     assert rc == 0, nat.load().vp_last_error()
 
@@ -255,5 +335,7 @@ def _ok(rc):
 if __name__ == "__main__":
     if sys.argv[1] == "pooler":
         pooler(sys.argv[2], control=sys.argv[3:] == ["control"])
+    elif sys.argv[1] == "gemm":
+        gemm(sys.argv[2:])
     else:
         {"tattn": tattn, "spatial": spatial, "attention": attention}[sys.argv[1]](sys.argv[2])

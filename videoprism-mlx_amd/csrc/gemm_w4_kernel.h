@@ -104,20 +104,29 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
   // when every XCD owns whole M-blocks): each XCD sweeps its M-blocks once per group of ngrp
   // N-tiles, so the group's W rows (<= 2.5 MB) stay in the XCD's 4 MiB L2 instead of the whole W
   // being re-fetched from beyond it for every M-block (ffn_layer1: W = 4.7 MB)
-  auto coords = [&](int t, int& tm, int& tn) {
-    if (ngrp == tilesN) {
-      tm = t / tilesN;
-      tn = t - tm * tilesN;
-      return;
+  // A tile index is a mixed-radix number: N-tile within its group (radix ngrp), M-block within the
+  // XCD (radix mbx; ungrouped: never wraps), group.  A workgroup's tiles are `stride` apart, so the
+  // digits of its first tile and of the stride are split off once (the only divisions) and the next
+  // tile follows by digit-wise addition with carries.  A grouped workgroup's tiles stay inside its
+  // XCD's range [x T/8, (x+1) T/8), so x (tm0 = x * mbx) is constant.  (tm, tn) = (tm0 + rm, gn + c).
+  struct TilePos { int c, rm, gn; };
+  const bool grouped = ngrp != tilesN;
+  const int mbx = grouped ? (M / BM) >> 3 : 0x7fffffff;
+  auto split = [&](int t, TilePos& p) -> int {
+    if (!grouped) {
+      p.rm = t / tilesN;
+      p.c = t - p.rm * tilesN;
+      p.gn = 0;
+      return 0;
     }
-    const int mbx = (M / BM) >> 3;
     const int x = t / (mbx * tilesN);
     const int u = t - x * mbx * tilesN;
     const int gsz = mbx * ngrp;
     const int gi = u / gsz, r = u - gi * gsz;
-    const int rm = r / ngrp;
-    tm = x * mbx + rm;
-    tn = gi * ngrp + (r - rm * ngrp);
+    p.rm = r / ngrp;
+    p.c = r - p.rm * ngrp;
+    p.gn = gi * ngrp;
+    return x * mbx;
   };
   const int G = gridDim.x;
   const int b = blockIdx.x;
@@ -134,6 +143,22 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
     count = b < T ? (T - b + G - 1) / G : 0;
   }
   if (count == 0) return;
+  TilePos t_cur, t_step;  // the compute stream's tile; the stride's digits
+  const int tm0 = split(first, t_cur);
+  split(stride, t_step);
+  auto next_tile = [&](TilePos& p) {
+    p.c += t_step.c;
+    if (p.c >= ngrp) {
+      p.c -= ngrp;
+      ++p.rm;
+    }
+    p.rm += t_step.rm;
+    if (p.rm >= mbx) {
+      p.rm -= mbx;
+      p.gn += ngrp;
+    }
+    p.gn += t_step.gn;
+  };
   const int lane = threadIdx.x & 63;
   const int w = wave_id();
   const int wm = w >> 1, wn = w & 1;
@@ -176,44 +201,83 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
   typedef __attribute__((address_space(3))) void lds_void;
   // load stream: K-tile ld_g -> (tile ld_tm/ld_tn, K-tile ld_kt); the tail re-loads the last
   // K-tile (harmless), so every wait count stays uniform
-  int ld_g = 0, ld_kt = 0, ld_tile = first;
-  int ld_tm, ld_tn;
-  coords(ld_tile, ld_tm, ld_tn);
+  int ld_g = 0, ld_kt = 0;
+  TilePos ld_pos = t_cur;
+  // Scalar byte offsets (the loads' soffset) of this wave's piece 0 of the load stream's K-tile;
+  // piece i + 1 follows piece i by a constant (a_step[i & 1], w_step), the next K-tile by a_kstep /
+  // one line, and only a tile change multiplies.  All of it is uint32 arithmetic, so every offset is
+  // the former per-piece product modulo 2^32.
+  //   A: (tm BM + 8 pc) a_rb + kt 128, pc = w*8 + i
+  //   AVID: tm frame_b + ((pc >> 1) av_p + kt) a_rb + (pc & 1) 8 prow_b  (piece pc: patch-grid row
+  //         pc >> 1, patches 8 (pc & 1) + 0..7)
+  //   ABLK: ((tm 16 + (pc >> 1)) (K >> 5) + 2 kt) 1024 + (pc & 1) 512  (piece rows 8 pc .. +7: block
+  //         row pc >> 1, half pc & 1; K-tile = blocks 2 kt, +1)
+  const uint32_t a_step[2] = {AVID ? 8 * prow_b : ABLK ? 512u : 8 * a_rb,
+                              AVID ? (uint32_t)av_p * a_rb - 8 * prow_b
+                                   : ABLK ? (uint32_t)(K >> 5) * 1024u - 512u : 8 * a_rb};
+  const uint32_t a_kstep = AVID ? a_rb : ABLK ? 2048u : (uint32_t)(BK * 2);
+  const uint32_t w_step = 8 * w_rb;
+  uint32_t ld_a, ld_w;
+  auto ld_tile_base = [&]() {
+    const uint32_t tm = (uint32_t)(tm0 + ld_pos.rm), tn = (uint32_t)(ld_pos.gn + ld_pos.c);
+    if constexpr (AVID) ld_a = tm * frame_b + (uint32_t)(w * 4 * av_p) * a_rb;
+    else if constexpr (ABLK) ld_a = (uint32_t)((tm * 16 + w * 4) * (K >> 5)) * 1024u;
+    else ld_a = (tm * BM + (uint32_t)w * 64) * a_rb;
+    ld_w = (tn * BN + (uint32_t)w * 64) * w_rb;
+  };
+  ld_tile_base();
   auto advance = [&]() {
     if (ld_g + 1 >= total) return;
     ++ld_g;
     if (++ld_kt == nk) {
       ld_kt = 0;
-      ld_tile += stride;
-      coords(ld_tile, ld_tm, ld_tn);
+      next_tile(ld_pos);
+      ld_tile_base();
+    } else {
+      ld_a += a_kstep;
+      ld_w += BK * 2;
     }
   };
   // LDS: 2 x [A | W] K-tile buffers; S3: A buffers 0..2 then W buffers 0..1
   auto a_buf = [&](int ai) { return smem + ai * (S3 ? kOp : kBuf); };
   auto w_buf = [&](int wi) { return smem + (S3 ? 3 * kOp + wi * kOp : wi * kBuf + kOp); };
   // p: 0..7 A pieces into A buffer `buf`, 8..15 W pieces into W buffer `buf`
-  auto stage_piece = [&](int buf, int p) {
+  // `so`: the running scalar offset of the operand's pieces (ld_a / ld_w at piece 0), stepped here to
+  // the next piece by one scalar add.  The empty asm keeps it a running SGPR (the compiler would
+  // otherwise hold eight row numbers and multiply each by the row pitch again for every piece of every
+  // K-tile).
+  // The LDS destination in M0 is written once per four pieces of a row-major operand: pieces 4j .. 4j+3
+  // go out with the instruction's immediate offset (i & 3) KiB, which moves the LDS address and the
+  // global one alike, so it is taken back out of the scalar offset (a row is at least 128 B, so the
+  // scalar offset of piece i is at least i KiB; the frame and row-blocked A pieces lie closer together
+  // and keep one M0 write each).
+  auto stage_piece = [&](int buf, int p, uint32_t& so) {
     const int i = p & 7;
-    char* dst = (p >= 8 ? w_buf(buf) : a_buf(buf)) + (w * 8 + i) * 1024;
+    const bool share = p >= 8 || (!AVID && !ABLK);
+    const int io = share ? (i & 3) * 1024 : 0;
+    const uint32_t fix = !share ? 0u : ((i + 1) & 3) ? 0u - 1024u : 3072u;  // piece i -> i + 1
+    char* dst = (p >= 8 ? w_buf(buf) : a_buf(buf)) + (w * 8 + i) * 1024 - io;
+    // (the builtin takes its immediate offset and cache policy as literals)
+#define VP_W4_DMA(rs, v, aux)                                                                             \
+  switch (io) {                                                                                           \
+    case 0: __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)dst, 16, v, so, 0, aux); break;       \
+    case 1024: __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)dst, 16, v, so, 1024, aux); break; \
+    case 2048: __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)dst, 16, v, so, 2048, aux); break; \
+    default: __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)dst, 16, v, so, 3072, aux); break;   \
+  }
     if (p < 8) {
-      uint32_t so;
-      if constexpr (AVID) {  // piece w*8+i: patch-grid row (w*8+i) >> 1, patches 8 ((w*8+i) & 1) + 0..7
-        const int pc = w * 8 + i;
-        so = (uint32_t)ld_tm * frame_b + (uint32_t)((pc >> 1) * av_p + ld_kt) * a_rb + (uint32_t)(pc & 1) * 8 * prow_b;
-      } else if constexpr (ABLK) {  // piece rows 8 pc .. +7: block row pc >> 1, half pc & 1; K-tile = blocks 2 kt, +1
-        const int pc = w * 8 + i;
-        so = (uint32_t)((ld_tm * 16 + (pc >> 1)) * (K >> 5) + 2 * ld_kt) * 1024u + (uint32_t)(pc & 1) * 512u;
+      if constexpr (EpiTraits<EPI>::kResidStream) {  // aux 2: nt
+        VP_W4_DMA(rsA, vA[i & 1], 2)
       } else {
-        so = (uint32_t)(ld_tm * BM + (w * 8 + i) * 8) * a_rb + ld_kt * (BK * 2);
+        VP_W4_DMA(rsA, vA[i & 1], 0)
       }
-      if constexpr (EpiTraits<EPI>::kResidStream)  // aux 2: nt
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)dst, 16, vA[i & 1], so, 0, 2);
-      else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void*)dst, 16, vA[i & 1], so, 0, 0);
+      if (i < 7) so += a_step[i & 1] + fix;
     } else {
-      const uint32_t so = (uint32_t)(ld_tn * BN + (w * 8 + i) * 8) * w_rb + ld_kt * (BK * 2);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_void*)dst, 16, vW[i & 1], so, 0, 0);
+      VP_W4_DMA(rsW, vW[i & 1], 0)
+      if (i < 7) so += w_step + fix;
     }
+#undef VP_W4_DMA
+    if (i < 7) asm("" : "+s"(so));
   };
 
   // ---- fragments: 16x16x32 operand = rows (lane&15), 16-byte chunk kh*4 + (lane>>4)
@@ -246,11 +310,12 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
 
   // ---- prologue: K-tiles 0, 1 into buffers 0, 1; fragments of (0, h0)
 #pragma unroll
-  for (int p = 0; p < 16; ++p) stage_piece(0, p);
-  advance();
+  for (int b2 = 0; b2 < 2; ++b2) {
+    uint32_t sa = ld_a, sw = ld_w;
 #pragma unroll
-  for (int p = 0; p < 16; ++p) stage_piece(1, p);
-  advance();
+    for (int p = 0; p < 16; ++p) stage_piece(b2, p, p < 8 ? sa : sw);
+    advance();
+  }
   asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
   sched_fence();
   __builtin_amdgcn_s_barrier();
@@ -259,15 +324,30 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
   for (int q = 0; q < 16; ++q) rd(0, 0, 0, q);
   int a3 = 0;  // S3: A buffer of the K-tile being computed (g % 3)
 
+  // One LDS wait per k-half: the hand-written lgkmcnt(0) that opens h0 / h1 retires the fragment set
+  // the phase consumes, but the compiler cannot see through it and would put its own counted
+  // lgkmcnt(N) in front of the phase's MFMAs as the other set's reads are issued among them (eight per
+  // k-half, none of which can wait).  Passing the whole set through one empty asm ends its tracking:
+  // the compiler puts a single lgkmcnt(0) of its own in front of that statement (beside the
+  // hand-written one, which stays: it also retires the reads of the buffer the h1 barrier frees) and the
+  // phase carries no further wait.  The reads issued in the phase (the other set) stay visible to it.
+  auto landed = [&](int set) {
+    asm volatile("" : "+v"(fw[set][0]), "+v"(fw[set][1]), "+v"(fw[set][2]), "+v"(fw[set][3]), "+v"(fw[set][4]),
+                      "+v"(fw[set][5]), "+v"(fw[set][6]), "+v"(fw[set][7]), "+v"(fa[set][0]), "+v"(fa[set][1]),
+                      "+v"(fa[set][2]), "+v"(fa[set][3]), "+v"(fa[set][4]), "+v"(fa[set][5]), "+v"(fa[set][6]),
+                      "+v"(fa[set][7]));
+  };
   auto h0 = [&](int cb, bool zero) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    landed(0);
     sched_fence();
     const int a_ld = a3 == 0 ? 2 : a3 - 1;  // S3: A buffer of K-tile g+2 (freed by K-tile g-1)
+    uint32_t sa = ld_a;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       rd(1, S3 ? a3 : cb, cb, q);
       if constexpr (S3) {
-        if (q < 8) stage_piece(a_ld, q);
+        if (q < 8) stage_piece(a_ld, q, sa);
       }
     }
 #pragma unroll
@@ -295,6 +375,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
     if constexpr (S3 && early) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
     else if constexpr (S3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    landed(1);
     sched_fence();
     mfma(1, 0, false);
     mfma(1, 1, false);
@@ -302,13 +383,14 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
     __builtin_amdgcn_s_barrier();
     sched_fence();
     const int an = a3 == 2 ? 0 : a3 + 1;  // S3: A buffer of K-tile g+1
+    uint32_t sa = ld_a, sw = ld_w;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       if constexpr (!defer) rd(0, S3 ? an : (cb ^ 1), cb ^ 1, q);
       if constexpr (S3) {
-        if (q >= 8) stage_piece(cb, q);  // W of K-tile g+2 into W buffer cb
+        if (q >= 8) stage_piece(cb, q, sw);  // W of K-tile g+2 into W buffer cb
       } else if constexpr (!(ABL & 4)) {
-        stage_piece(cb, q);
+        stage_piece(cb, q, q < 8 ? sa : sw);
       }
     }
 #pragma unroll
@@ -348,9 +430,9 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
     uint4 exr[2][2][2];   // kEarly: raw residual [buffer][nh][pass]
     int m0t = 0, n0t = 0;  // kEarly: this tile's wave origin (the epilogue's m0, n0)
     float keepb[8];       // EPI_GELU_BF16_LN_BLK with padded rows: 1 - rowpad of the same rows
+    if (j) next_tile(t_cur);
     {
-      int ttm, ttn;
-      coords(first + j * stride, ttm, ttn);
+      const int ttm = tm0 + t_cur.rm, ttn = t_cur.gn + t_cur.c;
       m0t = ttm * BM + wm * 128;
       n0t = ttn * BN + wn * 128;
       const int nb = ttn * BN + wn * 128 + es * 8;
@@ -430,8 +512,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_bf16_w4_kernel(
     if constexpr (ABL & 8) {
       if (ep.ldo != -12345) continue;  // never false at run time: keeps acc live, skips stores
     }
-    int etm, etn;
-    coords(first + j * stride, etm, etn);
+    const int etm = tm0 + t_cur.rm, etn = t_cur.gn + t_cur.c;
     const int m0 = etm * BM + wm * 128, n0 = etn * BN + wn * 128;
     using Tr = EpiTraits<EPI>;
     // S3: the A buffer of the tile's last K-tile (free since its h1 barrier; refilled in the next h0)
