@@ -22,6 +22,9 @@
  *  - vp_forward never allocates, never synchronises: all activations live in the caller's
  *    workspace (size from vp_workspace_bytes); the call is asynchronous on `stream` and
  *    can be captured into a hipGraph.
+ *  - A workspace is scratch: for every entry point that takes one, the bytes its *_workspace_bytes reports for the
+ *    same arguments are enough (the call writes nothing outside [workspace, workspace + bytes) and refuses a shorter
+ *    one with VP_EINVAL before its first launch), and no output bit depends on what the workspace held on entry.
  *  - A handle is bound to one device and is not thread-safe: calls on one handle must not overlap
  *    (in particular vp_prepare_geometry / vp_prepare_frames, which add to the handle's cached tables,
  *    must not run while vp_forward runs on the same handle).  Different handles -- on one device or
