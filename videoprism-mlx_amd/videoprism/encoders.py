@@ -54,18 +54,14 @@ def _profile_class_names() -> list:
     return names
 
 
-def _vp_config(cfg: dict, bf16: bool):
+def _vp_config(cfg: dict, fprop_code: int):
     return _native.vp_config(
         patch_size=cfg["patch_size"], pos_emb_t=cfg["pos_emb_shape"][0],
         pos_emb_h=cfg["pos_emb_shape"][1], pos_emb_w=cfg["pos_emb_shape"][2],
         model_dim=cfg["model_dim"], num_spatial_layers=cfg["num_spatial_layers"],
         num_temporal_layers=cfg["num_temporal_layers"], num_heads=cfg["num_heads"],
         mlp_dim=cfg["mlp_dim"], atten_logit_cap=float(cfg.get("atten_logit_cap", 0.0)),
-        fprop_dtype=_native.VP_BF16 if bf16 else _native.VP_F32)
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+        fprop_dtype=fprop_code)
 
 
 class FrameStates:
@@ -120,25 +116,43 @@ class FrameStates:
         return FrameStates(torch.cat([q.states for q in parts]), pads, first.frame_size)
 
 
-def _frames_on_device(frames, bf16: bool):
-    """[F, H, W, 3] frames as `apply` moves clips: numpy -> the current device (uint8 as bytes, anything else as
-    fp32), host tensors -> the current device, fp32 -> bf16 for a bf16 model.  -> (CUDA tensor, device index)."""
+def _pick_device(*arrays) -> int:
+    """The device a call runs on: that of a CUDA tensor among its array arguments (the last one given), otherwise
+    the current device.  Everything else is moved there."""
+    torch = _torch()
+    device = torch.cuda.current_device()
+    for t in arrays:
+        if isinstance(t, torch.Tensor) and t.is_cuda:
+            device = t.device.index
+    return device
+
+
+def _wants_numpy(*arrays) -> bool:
+    """Results are numpy arrays unless one of these arguments came as a torch tensor."""
+    torch = _torch()
+    return not any(isinstance(t, torch.Tensor) for t in arrays)
+
+
+def _frames_on_device(frames, rank: int, bf16: bool, device: int):
+    """Clips [B, T, H, W, 3] (rank 5) or frames [F, H, W, 3] (rank 4), numpy or torch, as a CUDA tensor on
+    cuda:`device`.  numpy uint8 travels as bytes (4x less H2D than fp32) and is normalised /255 on device exactly
+    as video_utils.py:94; any other numpy dtype goes as fp32; fp32 becomes bf16 for a bf16 model (colab usage:
+    inputs cast to the fprop dtype by the caller)."""
     torch = _torch()
     if isinstance(frames, torch.Tensor):
         x = frames
-        if not x.is_cuda:
-            x = x.to(f"cuda:{torch.cuda.current_device()}")
     else:
         arr = np.asarray(frames)
         x = torch.from_numpy(np.ascontiguousarray(arr if arr.dtype == np.uint8 else
                                                   arr.astype(np.float32, copy=False)))
-        x = x.to(f"cuda:{torch.cuda.current_device()}")
-    if x.dim() != 4:
-        raise ValueError(f"frames must be [F, H, W, 3], got {tuple(x.shape)}")
-    assert x.shape[1] == x.shape[2]  # encoders.py:435
+    x = x.to(f"cuda:{device}")
+    if x.dim() != rank:
+        raise ValueError(f"inputs must be [B, T, H, W, 3], got {tuple(x.shape)}" if rank == 5 else
+                         f"frames must be [F, H, W, 3], got {tuple(x.shape)}")
+    assert x.shape[-3] == x.shape[-2]  # encoders.py:435
     if bf16 and x.dtype == torch.float32:
         x = x.to(torch.bfloat16)
-    return x, x.device.index
+    return x
 
 
 class _CheckedIndex:
@@ -192,12 +206,63 @@ def _as_paddings(p):
     return torch.from_numpy(np.asarray(p, dtype=np.float32))
 
 
+def _encode_text(eng, ids, paddings, normalize: bool):
+    """Text ids and paddings [Q, L] (numpy or torch) on the engine's device -> eng.encode_text."""
+    torch = _torch()
+    assert paddings is not None, "Text paddings are required."
+    if not isinstance(ids, torch.Tensor):
+        ids = torch.from_numpy(np.asarray(ids, dtype=np.int32))
+    dev = f"cuda:{eng.device}"
+    return eng.encode_text(ids.to(dev), _as_paddings(paddings).to(dev), normalize)
+
+
+def _pack(primary, named, fprop_dtype, as_numpy: bool):
+    """What `apply` returns: the `primary` results (None stays None), then `outputs` built from the (name, buffer
+    or None) pairs whose buffer exists; every value cast to the fprop dtype (encoders.py:50-67 casts the normalised
+    fp32 vector back), and an fp32 numpy array if `as_numpy`."""
+    def cvt(t):
+        if t is None:
+            return None
+        t = t.to(fprop_dtype)
+        return t.float().cpu().numpy() if as_numpy else t
+    return (*(cvt(t) for t in primary), {k: cvt(v) for k, v in named if v is not None})
+
+
+def _c_args(args) -> list:
+    """C-ABI arguments: a tensor stands for its address."""
+    torch = _torch()
+    return [_native._ptr(a) if isinstance(a, torch.Tensor) else a for a in args]
+
+
+@dataclasses.dataclass
+class _Source:
+    """What a video forward reads, as `_check_video` (clips) or `_check_windows` (windows of frame states) found it
+    fit for the C-ABI.  Every engine has one entry point and one workspace query per kind of source: the entry
+    point takes (handle, *lead, B, T, H, W, fp, ...), the query (handle, B, T, H, W)."""
+
+    windows: bool  # which of the engine's two entry points and workspace queries
+    lead: tuple    # clips: (video, its dtype code); windows: (states [F, N, D], F, frame_index int32 [Wn, T])
+    B: int         # clips, or windows (Wn)
+    T: int
+    H: int
+    W: int
+    N: int         # tokens per frame
+    fp: Any        # frame paddings [B, T] fp32 on the device, or None
+    device: Any    # where the results are allocated
+
+    def __iter__(self):
+        """Unpacks as the C arguments in call order: for clips (video, dtype code, fp, B, T, H, W, N)."""
+        return iter((*self.lead, self.fp, self.B, self.T, self.H, self.W, self.N))
+
+
 class _EngineBase:
     """One native handle (packed weights on one device) plus its grow-only workspaces.  A subclass
     names its C entry points (`_PREFIX`_create / _set_param / _finalize / _destroy) and gives the
-    arguments of its create call ahead of (device, &handle)."""
+    arguments of its create call ahead of (device, &handle), and its video entry points and their
+    workspace queries as (over clips, over windows of frame states)."""
 
     _PREFIX = ""
+    _ENTRY = _QUERY = ("", "")
 
     def __init__(self, cfg: dict, flat_params: dict, device: int, bf16: bool):
         self.cfg = dict(cfg)
@@ -226,6 +291,16 @@ class _EngineBase:
 
     def _create_args(self) -> tuple:
         raise NotImplementedError
+
+    @property
+    def fprop_dtype(self):
+        """The model's fprop dtype as a torch dtype."""
+        return _torch().bfloat16 if self.bf16 else _torch().float32
+
+    @property
+    def fprop_code(self) -> int:
+        """The model's fprop dtype as the C-ABI's VP_* code."""
+        return _native.VP_BF16 if self.bf16 else _native.VP_F32
 
     def handle(self):
         """The native handle itself (vp_handle / vp_clip / vp_classifier), for the _native.dev_* entries."""
@@ -280,19 +355,16 @@ class _EngineBase:
         s = stream if stream is not None else _torch().cuda.current_stream(self.device)
         return ctypes.c_void_p(s.cuda_stream)
 
-    def _check_video(self, video, frame_paddings):
-        """-> (video as the C-ABI takes it, its dtype code, frame paddings [B, T] fp32 or None, B, T, H, W,
-        tokens per frame), with the positional tables for this frame size and clip length prepared."""
+    def _check_video(self, video, frame_paddings) -> _Source:
+        """The clips `video` [B, T, H, W, 3] and their frame paddings [B, T] or None as a _Source, with the
+        positional tables for this frame size and clip length prepared."""
         torch = _torch()
         if video.dim() != 5:
             raise ValueError(f"inputs must be [B, T, H, W, 3], got {tuple(video.shape)}")
         B, T, H, W, C = video.shape
         if C != 3:
             raise ValueError("inputs must have 3 channels")
-        P = self.cfg["patch_size"]
-        if H % P or W % P:
-            raise ValueError(f"Image height ({H}) and width ({W}) should be multiples "
-                             f"of patch_size ({P}).")
+        N = self._tokens_per_frame(H, W)
         _check_device(video, self.device, "video")
         video = video.contiguous()
         if video.dtype not in (torch.bfloat16, torch.float32, torch.uint8):
@@ -302,56 +374,58 @@ class _EngineBase:
             fp = frame_paddings.to(device=video.device, dtype=torch.float32).contiguous()
             if tuple(fp.shape) != (B, T):
                 raise AssertionError(f"frame_paddings.shape == {(B, T)} failed (encoders.py:442)")
-        # first sight of a frame size / clip length: the interpolated spatial (encoders.py:497-512) and
-        # temporal (:543-553) positional tables, cached on the device by the library (the forward
-        # itself never allocates)
+        self._prepare_tables(H, W, T)
+        # uint8 frames are normalised /255 on device
+        return _Source(False, (video, _native._prec(video)), B, T, H, W, N, fp, video.device)
+
+    def _tokens_per_frame(self, H: int, W: int) -> int:
+        P = self.cfg["patch_size"]
+        if H % P or W % P:
+            raise ValueError(f"Image height ({H}) and width ({W}) should be multiples of patch_size ({P}).")
+        return (H // P) * (W // P)
+
+    def _prepare_tables(self, H: int, W: int, T: int) -> None:
+        """First sight of a frame size / clip length: the interpolated spatial (encoders.py:497-512) and temporal
+        (:543-553) positional tables, cached on the device by the library (the forward itself never allocates)."""
         if (H, W) not in self._grids:
             _native.call("vp_prepare_geometry", self.video_handle(), H, W)
             self._grids.add((H, W))
         if T not in self._grids:
             _native.call("vp_prepare_frames", self.video_handle(), T)
             self._grids.add(T)
-        # uint8 frames are normalised /255 on device
-        return video, _native._prec(video), fp, B, T, H, W, (H // P) * (W // P)
 
     # -- sliding windows: per-frame states once, then windows of them -------------------
     def encode_frames(self, frames, frame_paddings=None, stream=None) -> FrameStates:
         """frames: CUDA tensor [F, H, W, 3] (fp32, bf16 or uint8) on this engine's device; frame_paddings [F] or
         None.  The spatial half of the encoder, once per frame (vp_forward_spatial)."""
-        torch = _torch()
         if frames.dim() != 4:
             raise ValueError(f"frames must be [F, H, W, 3], got {tuple(frames.shape)}")
-        fp = None if frame_paddings is None else frame_paddings.reshape(-1, 1)
-        video, in_dt, fp, F, _, H, W, N = self._check_video(frames.unsqueeze(1), fp)
-        states = torch.empty((F, N, self.cfg["model_dim"]), dtype=torch.bfloat16 if self.bf16 else torch.float32,
-                             device=video.device)
-        fp = None if fp is None else fp.reshape(F)
+        src = self._check_video(frames.unsqueeze(1), None if frame_paddings is None else frame_paddings.reshape(-1, 1))
+        F = src.B
+        states = _torch().empty((F, src.N, self.cfg["model_dim"]), dtype=self.fprop_dtype, device=src.device)
+        fp = None if src.fp is None else src.fp.reshape(F)
         if F > 0:
             vh = self.video_handle()
-            ws = self._workspace("spatial", "vp_spatial_workspace_bytes", F, H, W, handle=vh)
-            _native.call("vp_forward_spatial", vh, _ptr(video), in_dt, F, H, W, _ptr(fp), _ptr(states), _ptr(ws),
+            ws = self._workspace("spatial", "vp_spatial_workspace_bytes", F, src.H, src.W, handle=vh)
+            _native.call("vp_forward_spatial", vh, *_c_args(src.lead), F, src.H, src.W, *_c_args((fp, states, ws)),
                          ws.numel(), self._stream(stream))
-        return FrameStates(states, fp, (H, W))
+        return FrameStates(states, fp, (src.H, src.W))
 
-    def _check_windows(self, fs: FrameStates, frame_index):
-        """-> (states [F, N, D] contiguous, frame_index as device int32 [Wn, T], the windows' frame paddings [Wn, T]
-        fp32 or None, F, Wn, T, H, W, N), with the temporal table for T prepared.  A host frame_index is
-        range-checked (IndexError); a CUDA tensor is not, since that would synchronise: the kernel clamps it."""
+    def _check_windows(self, fs: FrameStates, frame_index) -> _Source:
+        """Windows `frame_index` [Wn, T] of the frame states `fs` as a _Source (the index as device int32, the
+        windows' frame paddings gathered), with the positional tables prepared.  A host frame_index is range-checked
+        (IndexError); a CUDA tensor is not, since that would synchronise: the kernel clamps it."""
         torch = _torch()
         if not isinstance(fs, FrameStates):
             raise TypeError("states must be the FrameStates that encode_frames returns")
         st = fs.states
         _check_device(st, self.device, "states")
         H, W = fs.frame_size
-        P, D = self.cfg["patch_size"], self.cfg["model_dim"]
-        if H % P or W % P:
-            raise ValueError(f"Image height ({H}) and width ({W}) should be multiples of patch_size ({P}).")
-        N = (H // P) * (W // P)
-        want = torch.bfloat16 if self.bf16 else torch.float32
+        N, D = self._tokens_per_frame(H, W), self.cfg["model_dim"]
         if st.dim() != 3 or tuple(st.shape[1:]) != (N, D):
             raise ValueError(f"states must be [F, {N}, {D}] for this model and frame size, got {tuple(st.shape)}")
-        if st.dtype != want:
-            raise ValueError(f"states must be {want} (this model's fprop dtype), got {st.dtype}")
+        if st.dtype != self.fprop_dtype:
+            raise ValueError(f"states must be {self.fprop_dtype} (this model's fprop dtype), got {st.dtype}")
         F = st.shape[0]
         idx = _frame_index(frame_index, F)
         if idx.is_cuda:
@@ -362,72 +436,65 @@ class _EngineBase:
         if fs.paddings is not None and Wn > 0:
             _check_device(fs.paddings, self.device, "states.paddings")
             fp = fs.paddings.to(torch.float32)[idx.clamp(0, F - 1).long()].contiguous()
-        if T not in self._grids:
-            _native.call("vp_prepare_frames", self.video_handle(), T)
-            self._grids.add(T)
-        if (H, W) not in self._grids:  # states carried over from another engine of the same model
-            _native.call("vp_prepare_geometry", self.video_handle(), H, W)
-            self._grids.add((H, W))
-        return st.contiguous(), idx, fp, F, Wn, T, H, W, N
+        self._prepare_tables(H, W, T)  # the frame size too: states carried over from another engine of the model
+        return _Source(True, (st.contiguous(), F, idx), Wn, T, H, W, N, fp, st.device)
 
-    def _features(self, want: bool, B: int, L: int, device):
-        """A [B, L, D] buffer in the fprop dtype for spatial / spatio-temporal features, if wanted."""
-        torch = _torch()
-        return torch.empty((B, L, self.cfg["model_dim"]), dtype=torch.bfloat16 if self.bf16 else torch.float32,
-                           device=device) if want else None
+    def _launch(self, src: _Source, *results, stream=None) -> None:
+        """This engine's entry point for `src` (_ENTRY, with its workspace query _QUERY: clips, windows):
+        (handle, *src.lead, B, T, H, W, frame paddings, *results, workspace, its size, stream)."""
+        dims = (src.B, src.T, src.H, src.W)
+        ws = self._workspace("video", self._QUERY[src.windows], *dims)
+        _native.call(self._ENTRY[src.windows], self._h, *_c_args(src.lead), *dims, *_c_args((src.fp, *results, ws)),
+                     ws.numel(), self._stream(stream))
+
+    def _features(self, want: bool, src: _Source):
+        """A [B, T*N, D] buffer in the fprop dtype for spatial / spatio-temporal features, if wanted."""
+        return _torch().empty((src.B, src.T * src.N, self.cfg["model_dim"]), dtype=self.fprop_dtype,
+                              device=src.device) if want else None
 
 
 class Engine(_EngineBase):
     """One vp_handle (packed weights on one device) plus a reusable workspace."""
 
     _PREFIX = "vp"
+    _ENTRY = ("vp_forward", "vp_forward_temporal")
+    _QUERY = ("vp_workspace_bytes", "vp_temporal_workspace_bytes")
 
     def _create_args(self):
-        return (ctypes.byref(_vp_config(self.cfg, self.bf16)),)
+        return (ctypes.byref(_vp_config(self.cfg, self.fprop_code)),)
 
     def video_handle(self):
         return self._h
 
     def workspace(self, B, T, H, W):
-        return self._workspace("video", "vp_workspace_bytes", B, T, H, W)
+        return self._workspace("video", self._QUERY[0], B, T, H, W)
+
+    def _run(self, src: _Source, out_dtype=None, want_spatial=False, out=None, stream=None):
+        """-> (embeddings [B, T*N, D], spatial features or None) of the clips or windows `src`."""
+        torch = _torch()
+        shape = (src.B, src.T * src.N, self.cfg["model_dim"])
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype or self.fprop_dtype, device=src.device)
+        else:  # the kernels write B*T*N*D elements through the raw pointer
+            _check_device(out, self.device, "out")
+            if tuple(out.shape) != shape or out.dtype not in (torch.bfloat16, torch.float32) \
+                    or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous bf16/fp32 tensor of shape {shape}, "
+                                 f"got {tuple(out.shape)} {out.dtype} contiguous={out.is_contiguous()}")
+        sp = torch.empty_like(out) if want_spatial else None
+        if src.B:  # otherwise an empty batch: the reference's zero-size result, nothing to launch
+            self._launch(src, out, _native._prec(out), sp, stream=stream)
+        return out, sp
 
     def forward(self, video, frame_paddings=None, out_dtype=None, want_spatial=False,
                 out=None, stream=None):
         """video: CUDA tensor [B,T,H,W,3] (fp32, bf16 or uint8) on this engine's device."""
-        torch = _torch()
-        video, in_dt, fp, B, T, H, W, N = self._check_video(video, frame_paddings)
-        out_dtype = out_dtype or (torch.bfloat16 if self.bf16 else torch.float32)
-        D = self.cfg["model_dim"]
-        if out is None:
-            out = torch.empty((B, T * N, D), dtype=out_dtype, device=video.device)
-        else:  # the kernels write B*T*N*D elements through the raw pointer
-            _check_device(out, self.device, "out")
-            if tuple(out.shape) != (B, T * N, D) or out.dtype not in (torch.bfloat16, torch.float32) \
-                    or not out.is_contiguous():
-                raise ValueError(f"out must be a contiguous bf16/fp32 tensor of shape {(B, T * N, D)}, "
-                                 f"got {tuple(out.shape)} {out.dtype} contiguous={out.is_contiguous()}")
-        sp = torch.empty_like(out) if want_spatial else None
-        if B == 0:  # an empty batch: the reference's zero-size result, nothing to launch
-            return out, sp
-        ws = self.workspace(B, T, H, W)
-        _native.call("vp_forward", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp), _ptr(out),
-                     _native._prec(out), _ptr(sp), _ptr(ws), ws.numel(), self._stream(stream))
-        return out, sp
+        return self._run(self._check_video(video, frame_paddings), out_dtype, want_spatial, out, stream)
 
     def forward_windows(self, fs: FrameStates, frame_index, out_dtype=None, want_spatial=False, stream=None):
         """The temporal half over windows of frame states (vp_forward_temporal): frame_index int [Wn, T] ->
         embeddings [Wn, T*N, D], bitwise `forward` on the gathered clips."""
-        torch = _torch()
-        st, idx, fp, F, Wn, T, H, W, N = self._check_windows(fs, frame_index)
-        out_dtype = out_dtype or (torch.bfloat16 if self.bf16 else torch.float32)
-        out = torch.empty((Wn, T * N, self.cfg["model_dim"]), dtype=out_dtype, device=st.device)
-        sp = torch.empty_like(out) if want_spatial else None
-        if Wn == 0:  # no windows: a zero-size result, nothing to launch
-            return out, sp
-        ws = self._workspace("video", "vp_temporal_workspace_bytes", Wn, T, H, W)
-        _native.call("vp_forward_temporal", self._h, _ptr(st), F, _ptr(idx), Wn, T, H, W, _ptr(fp), _ptr(out),
-                     _native._prec(out), _ptr(sp), _ptr(ws), ws.numel(), self._stream(stream))
-        return out, sp
+        return self._run(self._check_windows(fs, frame_index), out_dtype, want_spatial, None, stream)
 
 
 def _cached_engine(model, variables, device: int, norm_policy: str, make, policies=("pre",)):
@@ -449,8 +516,56 @@ def _cached_engine(model, variables, device: int, norm_policy: str, make, polici
     return eng
 
 
+class _VideoModel:
+    """What the three model dataclasses below share: the engine cache, the Flax-style `init`, `encode_frames`, the
+    `method=` refusal and the two ways a video reaches an engine (clips, windows of frame states).  A model adds
+    config(), param_specs(), engine(variables, device) and its `apply` / `apply_windows`, two entries into one
+    `_forward` over an engine and its _Source."""
+
+    def __post_init__(self):
+        self._engines: dict = {}
+
+    @property
+    def is_bf16(self) -> bool:
+        return _is_bf16_dtype(self.fprop_dtype)
+
+    def init(self, rng=0, inputs=None, train: bool = False, **kwargs) -> dict:
+        """Returns {'params': tree} for the seed that `rng` holds."""
+        del inputs, train, kwargs
+        return self._init(rng if isinstance(rng, int) else int(np.asarray(rng).ravel()[-1]))
+
+    def _init(self, seed: int) -> dict:
+        return params_lib.synthetic_params(self.config(), seed, specs=self.param_specs())
+
+    @staticmethod
+    def _refuse_method(entry: str, kwargs: dict) -> None:
+        if kwargs.get("method") not in (None,):
+            raise NotImplementedError(f"{entry}(method=...) is not supported")
+
+    def encode_frames(self, variables, frames, frame_paddings=None) -> FrameStates:
+        """The spatial half (encoders.py:459-478 and what feeds it) of `frames` [F, H, W, 3] (numpy or CUDA
+        tensor; fp32, bf16 or uint8), frame_paddings [F] or None, once per frame -> FrameStates for
+        `apply_windows`.  Overlapping windows of one long video share these states."""
+        device = _pick_device(frames)
+        x = _frames_on_device(frames, 4, self.is_bf16, device)
+        return self.engine(variables, device).encode_frames(x, _as_paddings(frame_paddings))
+
+    def _clips(self, variables, inputs, frame_paddings, device: int):
+        """-> (the engine on `device`, its _Source for the clips `inputs` [B, T, H, W, 3])."""
+        x = _frames_on_device(inputs, 5, self.is_bf16, device)
+        eng = self.engine(variables, device)
+        return eng, eng._check_video(x, _as_paddings(frame_paddings))
+
+    def _windows(self, variables, states: FrameStates, frame_index):
+        """-> (the engine on the states' device, its _Source for the windows `frame_index` of `states`).  A host
+        index is range-checked before an engine is built, and only here."""
+        index = _CheckedIndex(_frame_index(frame_index, len(states)), len(states))
+        eng = self.engine(variables, _states_device(states))
+        return eng, eng._check_windows(states, index)
+
+
 @dataclasses.dataclass
-class FactorizedEncoder:
+class FactorizedEncoder(_VideoModel):
     """encoders.py:391-408 attributes; `fprop_dtype` as set by models.get_model."""
 
     patch_size: int = 18
@@ -466,9 +581,6 @@ class FactorizedEncoder:
     fprop_dtype: Any = None
     dtype: Any = None
 
-    def __post_init__(self):
-        self._engines: dict = {}
-
     # -- config view ---------------------------------------------------------------
     def config(self) -> dict:
         return dict(patch_size=self.patch_size, pos_emb_shape=tuple(self.pos_emb_shape),
@@ -479,72 +591,25 @@ class FactorizedEncoder:
     def param_specs(self) -> dict:
         return params_lib.encoder_leaf_specs(self.config(), scan=True)
 
-    @property
-    def is_bf16(self) -> bool:
-        return _is_bf16_dtype(self.fprop_dtype)
-
-    # -- Flax-style API ------------------------------------------------------------
-    def init(self, rng=0, inputs=None, train: bool = False, **kwargs) -> dict:
-        """Returns {'params': tree} with Flax's initialiser distributions."""
-        del inputs, train, kwargs
-        seed = int(np.asarray(rng).ravel()[-1]) if not isinstance(rng, int) else rng
+    def _init(self, seed: int) -> dict:
+        """Flax's initialiser distributions."""
         return params_lib.flax_default_init(self.config(), seed)
 
     def engine(self, variables, device: int) -> Engine:
         return _cached_engine(self, variables, device, self.norm_policy,
                               lambda flat: Engine(self.config(), flat, device, self.is_bf16))
 
+    # -- Flax-style API ------------------------------------------------------------
     def apply(self, variables, inputs, train: bool = False,
               return_intermediate: bool | Collection[str] = False, frame_paddings=None,
               **kwargs):
         """encoders.py:411-456.  `train` has no effect at inference (dropouts are 0)."""
         del train
-        if kwargs.get("method") not in (None,):
-            raise NotImplementedError("apply(method=...) is not supported")
-        torch = _torch()
-        as_numpy = not isinstance(inputs, torch.Tensor)
-        if as_numpy:
-            arr = np.asarray(inputs)
-            # uint8 frames travel as bytes (4x less H2D than fp32) and are normalised /255 on
-            # device exactly as video_utils.py:94
-            x = torch.from_numpy(np.ascontiguousarray(arr if arr.dtype == np.uint8 else
-                                                      arr.astype(np.float32, copy=False)))
-            device = torch.cuda.current_device()
-            x = x.to(f"cuda:{device}")
-        else:
-            x = inputs
-            if not x.is_cuda:
-                x = x.to(f"cuda:{torch.cuda.current_device()}")
-            device = x.device.index
-        if x.dim() != 5:
-            raise ValueError(f"inputs must be [B, T, H, W, 3], got {tuple(x.shape)}")
-        b, t, h, w, _ = x.shape
-        assert h == w  # encoders.py:435
-        if self.is_bf16 and x.dtype == torch.float32:
-            x = x.to(torch.bfloat16)  # colab usage: inputs cast to fprop dtype by the caller
-        fp = None
-        if frame_paddings is not None:
-            fp = frame_paddings if isinstance(frame_paddings, torch.Tensor) else \
-                torch.from_numpy(np.asarray(frame_paddings, dtype=np.float32))
-        eng = self.engine(variables, device)
-        want_sp = _contains(return_intermediate, "spatial_features")
-        emb, sp = eng.forward(x, frame_paddings=fp, want_spatial=want_sp)
-        outputs = {}
-        if want_sp:
-            outputs["spatial_features"] = sp
-        if as_numpy:
-            emb = emb.float().cpu().numpy()
-            outputs = {k: v.float().cpu().numpy() for k, v in outputs.items()}
-        return emb, outputs
+        self._refuse_method("apply", kwargs)
+        return self._forward(*self._clips(variables, inputs, frame_paddings, _pick_device(inputs)),
+                             return_intermediate, _wants_numpy(inputs))
 
     __call__ = apply
-
-    def encode_frames(self, variables, frames, frame_paddings=None) -> FrameStates:
-        """The spatial half (encoders.py:459-478 and what feeds it) of `frames` [F, H, W, 3] (numpy or CUDA
-        tensor; fp32, bf16 or uint8), frame_paddings [F] or None, once per frame -> FrameStates for
-        `apply_windows`.  Overlapping windows of one long video share these states."""
-        x, device = _frames_on_device(frames, self.is_bf16)
-        return self.engine(variables, device).encode_frames(x, _as_paddings(frame_paddings))
 
     def apply_windows(self, variables, states: FrameStates, frame_index, train: bool = False,
                       return_intermediate: bool | Collection[str] = False):
@@ -556,72 +621,55 @@ class FactorizedEncoder:
         frame_index is a torch tensor.  For a short last window, keep one padded frame among the states and
         point the missing slots at it."""
         del train
-        torch = _torch()
-        as_numpy = not isinstance(frame_index, torch.Tensor)
-        frame_index = _CheckedIndex(_frame_index(frame_index, len(states)), len(states))
-        eng = self.engine(variables, _states_device(states))
-        want_sp = _contains(return_intermediate, "spatial_features")
-        emb, sp = eng.forward_windows(states, frame_index, want_spatial=want_sp)
-        outputs = {"spatial_features": sp} if want_sp else {}
-        if as_numpy:
-            emb = emb.float().cpu().numpy()
-            outputs = {k: v.float().cpu().numpy() for k, v in outputs.items()}
-        return emb, outputs
+        return self._forward(*self._windows(variables, states, frame_index), return_intermediate,
+                             _wants_numpy(frame_index))
+
+    def _forward(self, eng: Engine, src: _Source, return_intermediate, as_numpy: bool):
+        emb, sp = eng._run(src, want_spatial=_contains(return_intermediate, "spatial_features"))
+        return _pack((emb,), (("spatial_features", sp),), eng.fprop_dtype, as_numpy)
 
 
 class ClipEngine(_EngineBase):
     """One vp_clip handle (packed LvT weights on one device) plus reusable workspaces."""
 
     _PREFIX = "vp_clip"
+    _ENTRY = ("vp_clip_encode_video", "vp_clip_encode_video_windows")
+    _QUERY = ("vp_clip_video_workspace_bytes", "vp_clip_video_windows_workspace_bytes")
 
     def _create_args(self):
         cfg = self.cfg
         c = _native.vp_clip_config(
-            video=_vp_config(cfg, self.bf16), num_auxiliary_layers=cfg.get("num_auxiliary_layers", 0),
+            video=_vp_config(cfg, self.fprop_code), num_auxiliary_layers=cfg.get("num_auxiliary_layers", 0),
             vocabulary_size=cfg["vocabulary_size"],
             num_unimodal_layers=cfg["num_unimodal_layers"],
             enable_causal_atten=1 if cfg.get("enable_causal_atten", True) else 0,
             norm_policy=_native.NORM_POLICIES[cfg.get("norm_policy", "pre")])
         return (ctypes.byref(c),)
 
+    def _run(self, src: _Source, normalize=True, want_frames=False, want_spatial=False,
+             want_spatiotemporal=False, stream=None):
+        """-> (video embeddings [B, D] fp32, frame embeddings [B, T, D] fp32 or None, spatial and spatio-temporal
+        features or None) of the clips or windows `src`."""
+        torch = _torch()
+        D = self.cfg["model_dim"]
+        vemb = torch.empty((src.B, D), dtype=torch.float32, device=src.device)
+        femb = torch.empty((src.B, src.T, D), dtype=torch.float32, device=src.device) if want_frames else None
+        sp = self._features(want_spatial, src)
+        st = self._features(want_spatiotemporal, src)
+        if src.B:  # otherwise an empty batch: zero-size embeddings, nothing to launch
+            self._launch(src, 1 if normalize else 0, vemb, femb, sp, st, self.fprop_code, stream=stream)
+        return vemb, femb, sp, st
+
     def encode_video(self, video, frame_paddings=None, normalize=True, want_frames=False,
                      want_spatial=False, want_spatiotemporal=False, stream=None):
-        torch = _torch()
-        video, in_dt, fp, B, T, H, W, N = self._check_video(video, frame_paddings)
-        D = self.cfg["model_dim"]
-        dev = video.device
-        vemb = torch.empty((B, D), dtype=torch.float32, device=dev)
-        femb = torch.empty((B, T, D), dtype=torch.float32, device=dev) if want_frames else None
-        sp = self._features(want_spatial, B, T * N, dev)
-        st = self._features(want_spatiotemporal, B, T * N, dev)
-        if B == 0:  # an empty batch: zero-size embeddings, nothing to launch
-            return vemb, femb, sp, st
-        ws = self._workspace("video", "vp_clip_video_workspace_bytes", B, T, H, W)
-        _native.call("vp_clip_encode_video", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp),
-                     1 if normalize else 0, _ptr(vemb), _ptr(femb), _ptr(sp), _ptr(st),
-                     _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
-                     self._stream(stream))
-        return vemb, femb, sp, st
+        return self._run(self._check_video(video, frame_paddings), normalize, want_frames, want_spatial,
+                         want_spatiotemporal, stream)
 
     def encode_video_windows(self, fs: FrameStates, frame_index, normalize=True, want_frames=False,
                              want_spatial=False, want_spatiotemporal=False, stream=None):
         """encode_video over windows of the vision tower's frame states (vp_clip_encode_video_windows)."""
-        torch = _torch()
-        st_, idx, fp, F, Wn, T, H, W, N = self._check_windows(fs, frame_index)
-        D = self.cfg["model_dim"]
-        dev = st_.device
-        vemb = torch.empty((Wn, D), dtype=torch.float32, device=dev)
-        femb = torch.empty((Wn, T, D), dtype=torch.float32, device=dev) if want_frames else None
-        sp = self._features(want_spatial, Wn, T * N, dev)
-        st = self._features(want_spatiotemporal, Wn, T * N, dev)
-        if Wn == 0:
-            return vemb, femb, sp, st
-        ws = self._workspace("video", "vp_clip_video_windows_workspace_bytes", Wn, T, H, W)
-        _native.call("vp_clip_encode_video_windows", self._h, _ptr(st_), F, _ptr(idx), Wn, T, H, W, _ptr(fp),
-                     1 if normalize else 0, _ptr(vemb), _ptr(femb), _ptr(sp), _ptr(st),
-                     _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
-                     self._stream(stream))
-        return vemb, femb, sp, st
+        return self._run(self._check_windows(fs, frame_index), normalize, want_frames, want_spatial,
+                         want_spatiotemporal, stream)
 
     def encode_text(self, ids, paddings, normalize=True, stream=None):
         torch = _torch()
@@ -635,13 +683,13 @@ class ClipEngine(_EngineBase):
         if Q == 0 and L >= 1:  # no queries: a zero-size result, nothing to launch
             return out
         ws = self._workspace("text", "vp_clip_text_workspace_bytes", Q, L)
-        _native.call("vp_clip_encode_text", self._h, _ptr(ids), _ptr(pad), Q, L, 1 if normalize else 0,
-                     _ptr(out), _ptr(ws), ws.numel(), self._stream(stream))
+        _native.call("vp_clip_encode_text", self._h, *_c_args((ids, pad)), Q, L, 1 if normalize else 0,
+                     *_c_args((out, ws)), ws.numel(), self._stream(stream))
         return out
 
 
 @dataclasses.dataclass
-class FactorizedVideoCLIP:
+class FactorizedVideoCLIP(_VideoModel):
     """encoders.py:762-910 attributes (the LvT video-text model); `fprop_dtype` as set by
     models.get_model."""
 
@@ -662,9 +710,6 @@ class FactorizedVideoCLIP:
     fprop_dtype: Any = None
     dtype: Any = None
 
-    def __post_init__(self):
-        self._engines: dict = {}
-
     def config(self) -> dict:
         return dict(patch_size=self.patch_size, pos_emb_shape=tuple(self.pos_emb_shape),
                     num_spatial_layers=self.num_spatial_layers,
@@ -679,15 +724,6 @@ class FactorizedVideoCLIP:
     def param_specs(self) -> dict:
         return params_lib.clip_leaf_specs(self.config(), scan=True)
 
-    @property
-    def is_bf16(self) -> bool:
-        return _is_bf16_dtype(self.fprop_dtype)
-
-    def init(self, rng=0, inputs=None, train: bool = False, **kwargs) -> dict:
-        del inputs, train, kwargs
-        seed = int(np.asarray(rng).ravel()[-1]) if not isinstance(rng, int) else rng
-        return params_lib.synthetic_params(self.config(), seed, specs=self.param_specs())
-
     def engine(self, variables, device: int) -> ClipEngine:
         return _cached_engine(self, variables, device, self.norm_policy,
                               lambda flat: ClipEngine(self.config(), flat, device, self.is_bf16),
@@ -700,65 +736,16 @@ class FactorizedVideoCLIP:
         outputs).  Embeddings are returned in the fprop dtype (encoders.py:50-67 casts the
         normalised fp32 vector back)."""
         del train
-        if kwargs.get("method") not in (None,):
-            raise NotImplementedError("apply(method=...) is not supported")
-        torch = _torch()
-        as_numpy = not any(isinstance(t, torch.Tensor) for t in (inputs, text_token_ids)
-                           if t is not None)
-        device = torch.cuda.current_device()
-        for t in (inputs, text_token_ids):
-            if isinstance(t, torch.Tensor) and t.is_cuda:
-                device = t.device.index
-        eng = self.engine(variables, device)
-        dev = f"cuda:{device}"
-        fdt = torch.bfloat16 if self.is_bf16 else torch.float32
-        video_emb = text_emb = None
-        outputs = {}
+        self._refuse_method("apply", kwargs)
+        device = _pick_device(inputs, text_token_ids)
         if inputs is not None:
-            if isinstance(inputs, torch.Tensor):
-                x = inputs
-            else:
-                arr = np.asarray(inputs)
-                x = torch.from_numpy(np.ascontiguousarray(
-                    arr if arr.dtype == np.uint8 else arr.astype(np.float32, copy=False)))
-            x = x.to(dev)
-            if x.dim() != 5:
-                raise ValueError(f"inputs must be [B, T, H, W, 3], got {tuple(x.shape)}")
-            assert x.shape[2] == x.shape[3]  # encoders.py:435
-            if self.is_bf16 and x.dtype == torch.float32:
-                x = x.to(torch.bfloat16)
-            fp = None
-            if frame_paddings is not None:
-                fp = frame_paddings if isinstance(frame_paddings, torch.Tensor) else \
-                    torch.from_numpy(np.asarray(frame_paddings, dtype=np.float32))
-            vemb, femb, sp, st = eng.encode_video(
-                x, fp, normalize, want_frames=_contains(return_intermediate, "frame_embeddings"),
-                want_spatial=_contains(return_intermediate, "spatial_features"),
-                want_spatiotemporal=_contains(return_intermediate, "spatiotemporal_features"))
-            video_emb = vemb.to(fdt)
-            for k, v in (("spatial_features", sp), ("spatiotemporal_features", st),
-                         ("frame_embeddings", femb)):
-                if v is not None:
-                    outputs[k] = v.to(fdt)
-        if text_token_ids is not None:
-            assert text_paddings is not None, "Text paddings are required."
-            ids = text_token_ids if isinstance(text_token_ids, torch.Tensor) else \
-                torch.from_numpy(np.asarray(text_token_ids, dtype=np.int32))
-            pads = text_paddings if isinstance(text_paddings, torch.Tensor) else \
-                torch.from_numpy(np.asarray(text_paddings, dtype=np.float32))
-            text_emb = eng.encode_text(ids.to(dev), pads.to(dev), normalize).to(fdt)
-        if as_numpy:
-            cvt = lambda t: None if t is None else t.float().cpu().numpy()  # noqa: E731
-            video_emb, text_emb = cvt(video_emb), cvt(text_emb)
-            outputs = {k: cvt(v) for k, v in outputs.items()}
-        return video_emb, text_emb, outputs
+            eng, src = self._clips(variables, inputs, frame_paddings, device)
+        else:
+            eng, src = self.engine(variables, device), None
+        return self._forward(eng, src, text_token_ids, text_paddings, normalize, return_intermediate,
+                             _wants_numpy(inputs, text_token_ids))
 
     __call__ = apply
-
-    def encode_frames(self, variables, frames, frame_paddings=None) -> FrameStates:
-        """FactorizedEncoder.encode_frames on the vision tower."""
-        x, device = _frames_on_device(frames, self.is_bf16)
-        return self.engine(variables, device).encode_frames(x, _as_paddings(frame_paddings))
 
     def apply_windows(self, variables, states: FrameStates = None, frame_index=None, text_token_ids=None,
                       text_paddings=None, train: bool = False, normalize: bool = True,
@@ -768,114 +755,78 @@ class FactorizedVideoCLIP:
         text inputs may be None as in `apply`.  Results are numpy arrays unless frame_index or text_token_ids is a
         torch tensor."""
         del train
-        if kwargs.get("method") not in (None,):
-            raise NotImplementedError("apply_windows(method=...) is not supported")
-        torch = _torch()
-        as_numpy = not any(isinstance(t, torch.Tensor) for t in (frame_index, text_token_ids) if t is not None)
+        self._refuse_method("apply_windows", kwargs)
         if states is not None:
             assert frame_index is not None, "frame_index is required with states."
-            frame_index = _CheckedIndex(_frame_index(frame_index, len(states)), len(states))
-            device = _states_device(states)
-        elif isinstance(text_token_ids, torch.Tensor) and text_token_ids.is_cuda:
-            device = text_token_ids.device.index
+            eng, src = self._windows(variables, states, frame_index)
         else:
-            device = torch.cuda.current_device()
-        eng = self.engine(variables, device)
-        dev = f"cuda:{device}"
-        fdt = torch.bfloat16 if self.is_bf16 else torch.float32
-        video_emb = text_emb = None
-        outputs = {}
-        if states is not None:
-            vemb, femb, sp, st = eng.encode_video_windows(
-                states, frame_index, normalize, want_frames=_contains(return_intermediate, "frame_embeddings"),
+            eng, src = self.engine(variables, _pick_device(text_token_ids)), None
+        return self._forward(eng, src, text_token_ids, text_paddings, normalize, return_intermediate,
+                             _wants_numpy(frame_index, text_token_ids))
+
+    def _forward(self, eng: ClipEngine, src: _Source | None, text_token_ids, text_paddings, normalize: bool,
+                 return_intermediate, as_numpy: bool):
+        """The video side over `src` and the text side over the ids, either of which may be None."""
+        vemb = femb = sp = st = temb = None
+        if src is not None:
+            vemb, femb, sp, st = eng._run(
+                src, normalize, want_frames=_contains(return_intermediate, "frame_embeddings"),
                 want_spatial=_contains(return_intermediate, "spatial_features"),
                 want_spatiotemporal=_contains(return_intermediate, "spatiotemporal_features"))
-            video_emb = vemb.to(fdt)
-            for k, v in (("spatial_features", sp), ("spatiotemporal_features", st),
-                         ("frame_embeddings", femb)):
-                if v is not None:
-                    outputs[k] = v.to(fdt)
         if text_token_ids is not None:
-            assert text_paddings is not None, "Text paddings are required."
-            ids = text_token_ids if isinstance(text_token_ids, torch.Tensor) else \
-                torch.from_numpy(np.asarray(text_token_ids, dtype=np.int32))
-            pads = text_paddings if isinstance(text_paddings, torch.Tensor) else \
-                torch.from_numpy(np.asarray(text_paddings, dtype=np.float32))
-            text_emb = eng.encode_text(ids.to(dev), pads.to(dev), normalize).to(fdt)
-        if as_numpy:
-            cvt = lambda t: None if t is None else t.float().cpu().numpy()  # noqa: E731
-            video_emb, text_emb = cvt(video_emb), cvt(text_emb)
-            outputs = {k: cvt(v) for k, v in outputs.items()}
-        return video_emb, text_emb, outputs
+            temb = _encode_text(eng, text_token_ids, text_paddings, normalize)
+        return _pack((vemb, temb), (("spatial_features", sp), ("spatiotemporal_features", st),
+                                    ("frame_embeddings", femb)), eng.fprop_dtype, as_numpy)
 
 
 class ClassifierEngine(_EngineBase):
     """One vp_classifier handle (FactorizedVideoClassifier weights on one device)."""
 
     _PREFIX = "vp_classifier"
+    _ENTRY = ("vp_classifier_forward", "vp_classifier_forward_windows")
+    _QUERY = ("vp_classifier_workspace_bytes", "vp_classifier_windows_workspace_bytes")
 
     def __init__(self, cfg: dict, num_classes: int, flat_params: dict, device: int, bf16: bool):
         self.num_classes = num_classes
         super().__init__(cfg, flat_params, device, bf16)
 
     def _create_args(self):
-        return (ctypes.byref(_vp_config(self.cfg, self.bf16)), self.num_classes)
+        return (ctypes.byref(_vp_config(self.cfg, self.fprop_code)), self.num_classes)
+
+    def _run(self, src: _Source, want_embeddings=False, want_spatial=False, want_spatiotemporal=False,
+             stream=None):
+        """-> (logits [B, num_classes] fp32, global embeddings [B, D] fp32 or None, spatial and spatio-temporal
+        features or None) of the clips or windows `src`."""
+        torch = _torch()
+        logits = torch.empty((src.B, self.num_classes), dtype=torch.float32, device=src.device)
+        emb = torch.empty((src.B, self.cfg["model_dim"]), dtype=torch.float32, device=src.device) \
+            if want_embeddings else None
+        sp = self._features(want_spatial, src)
+        st = self._features(want_spatiotemporal, src)
+        if src.B:  # otherwise an empty batch: zero-size logits, nothing to launch
+            self._launch(src, logits, emb, sp, st, self.fprop_code, stream=stream)
+        return logits, emb, sp, st
 
     def forward(self, video, frame_paddings=None, want_embeddings=False, want_spatial=False,
                 want_spatiotemporal=False, stream=None):
-        torch = _torch()
-        video, in_dt, fp, B, T, H, W, N = self._check_video(video, frame_paddings)
-        D = self.cfg["model_dim"]
-        dev = video.device
-        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
-        emb = torch.empty((B, D), dtype=torch.float32, device=dev) if want_embeddings else None
-        sp = self._features(want_spatial, B, T * N, dev)
-        st = self._features(want_spatiotemporal, B, T * N, dev)
-        if B == 0:  # an empty batch: zero-size logits, nothing to launch
-            return logits, emb, sp, st
-        ws = self._workspace("video", "vp_classifier_workspace_bytes", B, T, H, W)
-        _native.call("vp_classifier_forward", self._h, _ptr(video), in_dt, B, T, H, W, _ptr(fp),
-                     _ptr(logits), _ptr(emb), _ptr(sp), _ptr(st),
-                     _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
-                     self._stream(stream))
-        return logits, emb, sp, st
+        return self._run(self._check_video(video, frame_paddings), want_embeddings, want_spatial,
+                         want_spatiotemporal, stream)
 
     def forward_windows(self, fs: FrameStates, frame_index, want_embeddings=False, want_spatial=False,
                         want_spatiotemporal=False, stream=None):
         """forward over windows of the encoder's frame states (vp_classifier_forward_windows)."""
-        torch = _torch()
-        st_, idx, fp, F, Wn, T, H, W, N = self._check_windows(fs, frame_index)
-        D = self.cfg["model_dim"]
-        dev = st_.device
-        logits = torch.empty((Wn, self.num_classes), dtype=torch.float32, device=dev)
-        emb = torch.empty((Wn, D), dtype=torch.float32, device=dev) if want_embeddings else None
-        sp = self._features(want_spatial, Wn, T * N, dev)
-        st = self._features(want_spatiotemporal, Wn, T * N, dev)
-        if Wn == 0:
-            return logits, emb, sp, st
-        ws = self._workspace("video", "vp_classifier_windows_workspace_bytes", Wn, T, H, W)
-        _native.call("vp_classifier_forward_windows", self._h, _ptr(st_), F, _ptr(idx), Wn, T, H, W, _ptr(fp),
-                     _ptr(logits), _ptr(emb), _ptr(sp), _ptr(st),
-                     _native.VP_BF16 if self.bf16 else _native.VP_F32, _ptr(ws), ws.numel(),
-                     self._stream(stream))
-        return logits, emb, sp, st
+        return self._run(self._check_windows(fs, frame_index), want_embeddings, want_spatial,
+                         want_spatiotemporal, stream)
 
 
 @dataclasses.dataclass
-class FactorizedVideoClassifier:
+class FactorizedVideoClassifier(_VideoModel):
     """encoders.py:583-653: `encoder_params` (a FactorizedEncoder config) and `num_classes`."""
 
     encoder_params: dict = dataclasses.field(default_factory=dict)
     num_classes: int = 0
     fprop_dtype: Any = None
     dtype: Any = None
-
-    def __post_init__(self):
-        self._engines: dict = {}
-
-    @property
-    def is_bf16(self) -> bool:
-        return _is_bf16_dtype(self.fprop_dtype)
 
     def config(self) -> dict:
         c = {k: v for k, v in self.encoder_params.items() if k not in ("scan", "norm_policy")}
@@ -884,11 +835,6 @@ class FactorizedVideoClassifier:
 
     def param_specs(self) -> dict:
         return params_lib.classifier_leaf_specs(self.config(), self.num_classes, scan=True)
-
-    def init(self, rng=0, inputs=None, train: bool = False, **kwargs) -> dict:
-        del inputs, train, kwargs
-        seed = int(np.asarray(rng).ravel()[-1]) if not isinstance(rng, int) else rng
-        return params_lib.synthetic_params(self.config(), seed, specs=self.param_specs())
 
     def engine(self, variables, device: int) -> ClassifierEngine:
         return _cached_engine(
@@ -899,73 +845,24 @@ class FactorizedVideoClassifier:
               return_intermediate: bool | Collection[str] = False, frame_paddings=None, **kwargs):
         """encoders.py:594-653 -> (logits [B, num_classes], outputs)."""
         del train
-        if kwargs.get("method") not in (None,):
-            raise NotImplementedError("apply(method=...) is not supported")
-        torch = _torch()
-        as_numpy = not isinstance(inputs, torch.Tensor)
-        if as_numpy:
-            arr = np.asarray(inputs)
-            x = torch.from_numpy(np.ascontiguousarray(
-                arr if arr.dtype == np.uint8 else arr.astype(np.float32, copy=False)))
-            device = torch.cuda.current_device()
-        else:
-            x = inputs
-            device = x.device.index if x.is_cuda else torch.cuda.current_device()
-        x = x.to(f"cuda:{device}")
-        if x.dim() != 5:
-            raise ValueError(f"inputs must be [B, T, H, W, 3], got {tuple(x.shape)}")
-        assert x.shape[2] == x.shape[3]  # encoders.py:435
-        if self.is_bf16 and x.dtype == torch.float32:
-            x = x.to(torch.bfloat16)
-        fp = None
-        if frame_paddings is not None:
-            fp = frame_paddings if isinstance(frame_paddings, torch.Tensor) else \
-                torch.from_numpy(np.asarray(frame_paddings, dtype=np.float32))
-        eng = self.engine(variables, device)
-        logits, emb, sp, st = eng.forward(
-            x, fp, want_embeddings=_contains(return_intermediate, "global_embeddings"),
-            want_spatial=_contains(return_intermediate, "spatial_features"),
-            want_spatiotemporal=_contains(return_intermediate, "spatiotemporal_features"))
-        fdt = torch.bfloat16 if self.is_bf16 else torch.float32
-        logits = logits.to(fdt)
-        outputs = {}
-        for k, v in (("spatial_features", sp), ("spatiotemporal_features", st),
-                     ("global_embeddings", emb)):
-            if v is not None:
-                outputs[k] = v.to(fdt)
-        if as_numpy:
-            logits = logits.float().cpu().numpy()
-            outputs = {k: v.float().cpu().numpy() for k, v in outputs.items()}
-        return logits, outputs
+        self._refuse_method("apply", kwargs)
+        return self._forward(*self._clips(variables, inputs, frame_paddings, _pick_device(inputs)),
+                             return_intermediate, _wants_numpy(inputs))
 
     __call__ = apply
-
-    def encode_frames(self, variables, frames, frame_paddings=None) -> FrameStates:
-        """FactorizedEncoder.encode_frames on the classifier's encoder."""
-        x, device = _frames_on_device(frames, self.is_bf16)
-        return self.engine(variables, device).encode_frames(x, _as_paddings(frame_paddings))
 
     def apply_windows(self, variables, states: FrameStates, frame_index, train: bool = False,
                       return_intermediate: bool | Collection[str] = False):
         """`apply` over windows of frame states (FactorizedEncoder.apply_windows) -> (logits [Wn, num_classes],
         outputs)."""
         del train
-        torch = _torch()
-        as_numpy = not isinstance(frame_index, torch.Tensor)
-        frame_index = _CheckedIndex(_frame_index(frame_index, len(states)), len(states))
-        eng = self.engine(variables, _states_device(states))
-        logits, emb, sp, st = eng.forward_windows(
-            states, frame_index, want_embeddings=_contains(return_intermediate, "global_embeddings"),
+        return self._forward(*self._windows(variables, states, frame_index), return_intermediate,
+                             _wants_numpy(frame_index))
+
+    def _forward(self, eng: ClassifierEngine, src: _Source, return_intermediate, as_numpy: bool):
+        logits, emb, sp, st = eng._run(
+            src, want_embeddings=_contains(return_intermediate, "global_embeddings"),
             want_spatial=_contains(return_intermediate, "spatial_features"),
             want_spatiotemporal=_contains(return_intermediate, "spatiotemporal_features"))
-        fdt = torch.bfloat16 if self.is_bf16 else torch.float32
-        logits = logits.to(fdt)
-        outputs = {}
-        for k, v in (("spatial_features", sp), ("spatiotemporal_features", st),
-                     ("global_embeddings", emb)):
-            if v is not None:
-                outputs[k] = v.to(fdt)
-        if as_numpy:
-            logits = logits.float().cpu().numpy()
-            outputs = {k: v.float().cpu().numpy() for k, v in outputs.items()}
-        return logits, outputs
+        return _pack((logits,), (("spatial_features", sp), ("spatiotemporal_features", st),
+                                 ("global_embeddings", emb)), eng.fprop_dtype, as_numpy)
