@@ -9,6 +9,7 @@ in the HIP kernels behind the C-ABI; this file only moves parameters and buffers
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import dataclasses
 import weakref
@@ -259,7 +260,8 @@ class _EngineBase:
     """One native handle (packed weights on one device) plus its grow-only workspaces.  A subclass
     names its C entry points (`_PREFIX`_create / _set_param / _finalize / _destroy) and gives the
     arguments of its create call ahead of (device, &handle), and its video entry points and their
-    workspace queries as (over clips, over windows of frame states)."""
+    workspace queries as (over clips, over windows of frame states).  Every public call takes `stream=`:
+    with it, all device work of the call is ordered on that stream (`_ordered_on`)."""
 
     _PREFIX = ""
     _ENTRY = _QUERY = ("", "")
@@ -355,6 +357,15 @@ class _EngineBase:
         s = stream if stream is not None else _torch().cuda.current_stream(self.device)
         return ctypes.c_void_p(s.cuda_stream)
 
+    def _ordered_on(self, stream):
+        """The context every public call of an engine runs in.  With `stream=` given, all device work of the call is
+        ordered on that stream: the engine's own torch operations (casts, .contiguous(), the gather of the windows'
+        paddings), the allocation of the results and of a regrown workspace, and the native launches.  The inputs
+        only have to be ready on `stream`, whatever torch's current stream is, and the returned tensors belong to
+        `stream`: a consumer on another stream waits for it (and calls Tensor.record_stream) as for any tensor made
+        on a side stream.  With stream=None nothing is entered: the call runs on torch's current stream."""
+        return contextlib.nullcontext() if stream is None else _torch().cuda.stream(stream)
+
     def _check_video(self, video, frame_paddings) -> _Source:
         """The clips `video` [B, T, H, W, 3] and their frame paddings [B, T] or None as a _Source, with the
         positional tables for this frame size and clip length prepared."""
@@ -400,15 +411,17 @@ class _EngineBase:
         None.  The spatial half of the encoder, once per frame (vp_forward_spatial)."""
         if frames.dim() != 4:
             raise ValueError(f"frames must be [F, H, W, 3], got {tuple(frames.shape)}")
-        src = self._check_video(frames.unsqueeze(1), None if frame_paddings is None else frame_paddings.reshape(-1, 1))
-        F = src.B
-        states = _torch().empty((F, src.N, self.cfg["model_dim"]), dtype=self.fprop_dtype, device=src.device)
-        fp = None if src.fp is None else src.fp.reshape(F)
-        if F > 0:
-            vh = self.video_handle()
-            ws = self._workspace("spatial", "vp_spatial_workspace_bytes", F, src.H, src.W, handle=vh)
-            _native.call("vp_forward_spatial", vh, *_c_args(src.lead), F, src.H, src.W, *_c_args((fp, states, ws)),
-                         ws.numel(), self._stream(stream))
+        with self._ordered_on(stream):
+            src = self._check_video(frames.unsqueeze(1),
+                                    None if frame_paddings is None else frame_paddings.reshape(-1, 1))
+            F = src.B
+            states = _torch().empty((F, src.N, self.cfg["model_dim"]), dtype=self.fprop_dtype, device=src.device)
+            fp = None if src.fp is None else src.fp.reshape(F)
+            if F > 0:
+                vh = self.video_handle()
+                ws = self._workspace("spatial", "vp_spatial_workspace_bytes", F, src.H, src.W, handle=vh)
+                _native.call("vp_forward_spatial", vh, *_c_args(src.lead), F, src.H, src.W,
+                             *_c_args((fp, states, ws)), ws.numel(), self._stream(stream))
         return FrameStates(states, fp, (src.H, src.W))
 
     def _check_windows(self, fs: FrameStates, frame_index) -> _Source:
@@ -488,13 +501,16 @@ class Engine(_EngineBase):
 
     def forward(self, video, frame_paddings=None, out_dtype=None, want_spatial=False,
                 out=None, stream=None):
-        """video: CUDA tensor [B,T,H,W,3] (fp32, bf16 or uint8) on this engine's device."""
-        return self._run(self._check_video(video, frame_paddings), out_dtype, want_spatial, out, stream)
+        """video: CUDA tensor [B,T,H,W,3] (fp32, bf16 or uint8) on this engine's device.  stream: see
+        _EngineBase._ordered_on (all device work of the call, the results' allocation included, is on it)."""
+        with self._ordered_on(stream):
+            return self._run(self._check_video(video, frame_paddings), out_dtype, want_spatial, out, stream)
 
     def forward_windows(self, fs: FrameStates, frame_index, out_dtype=None, want_spatial=False, stream=None):
         """The temporal half over windows of frame states (vp_forward_temporal): frame_index int [Wn, T] ->
         embeddings [Wn, T*N, D], bitwise `forward` on the gathered clips."""
-        return self._run(self._check_windows(fs, frame_index), out_dtype, want_spatial, None, stream)
+        with self._ordered_on(stream):
+            return self._run(self._check_windows(fs, frame_index), out_dtype, want_spatial, None, stream)
 
 
 def _cached_engine(model, variables, device: int, norm_policy: str, make, policies=("pre",)):
@@ -662,29 +678,32 @@ class ClipEngine(_EngineBase):
 
     def encode_video(self, video, frame_paddings=None, normalize=True, want_frames=False,
                      want_spatial=False, want_spatiotemporal=False, stream=None):
-        return self._run(self._check_video(video, frame_paddings), normalize, want_frames, want_spatial,
-                         want_spatiotemporal, stream)
+        with self._ordered_on(stream):
+            return self._run(self._check_video(video, frame_paddings), normalize, want_frames, want_spatial,
+                             want_spatiotemporal, stream)
 
     def encode_video_windows(self, fs: FrameStates, frame_index, normalize=True, want_frames=False,
                              want_spatial=False, want_spatiotemporal=False, stream=None):
         """encode_video over windows of the vision tower's frame states (vp_clip_encode_video_windows)."""
-        return self._run(self._check_windows(fs, frame_index), normalize, want_frames, want_spatial,
-                         want_spatiotemporal, stream)
+        with self._ordered_on(stream):
+            return self._run(self._check_windows(fs, frame_index), normalize, want_frames, want_spatial,
+                             want_spatiotemporal, stream)
 
     def encode_text(self, ids, paddings, normalize=True, stream=None):
         torch = _torch()
         Q, L = ids.shape
         _check_device(ids, self.device, "text_token_ids")
-        ids = ids.to(dtype=torch.int32).contiguous()
-        pad = paddings.to(device=ids.device, dtype=torch.float32).contiguous()
-        if tuple(pad.shape) != (Q, L):
-            raise ValueError(f"text_paddings must be [{Q}, {L}], got {tuple(pad.shape)}")
-        out = torch.empty((Q, self.cfg["model_dim"]), dtype=torch.float32, device=ids.device)
-        if Q == 0 and L >= 1:  # no queries: a zero-size result, nothing to launch
-            return out
-        ws = self._workspace("text", "vp_clip_text_workspace_bytes", Q, L)
-        _native.call("vp_clip_encode_text", self._h, *_c_args((ids, pad)), Q, L, 1 if normalize else 0,
-                     *_c_args((out, ws)), ws.numel(), self._stream(stream))
+        with self._ordered_on(stream):
+            ids = ids.to(dtype=torch.int32).contiguous()
+            pad = paddings.to(device=ids.device, dtype=torch.float32).contiguous()
+            if tuple(pad.shape) != (Q, L):
+                raise ValueError(f"text_paddings must be [{Q}, {L}], got {tuple(pad.shape)}")
+            out = torch.empty((Q, self.cfg["model_dim"]), dtype=torch.float32, device=ids.device)
+            if Q == 0 and L >= 1:  # no queries: a zero-size result, nothing to launch
+                return out
+            ws = self._workspace("text", "vp_clip_text_workspace_bytes", Q, L)
+            _native.call("vp_clip_encode_text", self._h, *_c_args((ids, pad)), Q, L, 1 if normalize else 0,
+                         *_c_args((out, ws)), ws.numel(), self._stream(stream))
         return out
 
 
@@ -809,14 +828,16 @@ class ClassifierEngine(_EngineBase):
 
     def forward(self, video, frame_paddings=None, want_embeddings=False, want_spatial=False,
                 want_spatiotemporal=False, stream=None):
-        return self._run(self._check_video(video, frame_paddings), want_embeddings, want_spatial,
-                         want_spatiotemporal, stream)
+        with self._ordered_on(stream):
+            return self._run(self._check_video(video, frame_paddings), want_embeddings, want_spatial,
+                             want_spatiotemporal, stream)
 
     def forward_windows(self, fs: FrameStates, frame_index, want_embeddings=False, want_spatial=False,
                         want_spatiotemporal=False, stream=None):
         """forward over windows of the encoder's frame states (vp_classifier_forward_windows)."""
-        return self._run(self._check_windows(fs, frame_index), want_embeddings, want_spatial,
-                         want_spatiotemporal, stream)
+        with self._ordered_on(stream):
+            return self._run(self._check_windows(fs, frame_index), want_embeddings, want_spatial,
+                             want_spatiotemporal, stream)
 
 
 @dataclasses.dataclass
