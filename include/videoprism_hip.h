@@ -412,7 +412,18 @@ int vp_classifier_forward_windows(vp_classifier* c, const void* states, int64_t 
  *   vp_op_probe_backward  dlogits [B, C] fp32 -> every member of `grads` (all required; key_b's gradient is
  *                         exactly zero: the key bias cancels in the softmax).  `ws` is the workspace the forward
  *                         of the same params, tokens, B and S filled; it may be called more than once on it.
- * Equal inputs give equal bits: no sum is formed with atomics.  The tokens are read twice by each call. */
+ * Equal inputs give equal bits: no sum is formed with atomics.  The tokens are read twice by each call.
+ *
+ * Token paddings (vp_op_probe_forward_masked / vp_op_probe_backward_masked): `paddings` is a DEVICE fp32 [B, S], a
+ * token is padded iff its value is > 0.5 (AttenTokenPoolingLayer's `paddings`, layers.py:1103-1106), in any pattern,
+ * so clips of different lengths share one batch.  A padded token's logit becomes -0.7 * FLT_MAX in every head before
+ * the fp32 softmax.  In a clip with a valid token its probability is exactly 0, its row of `tokens` is never read
+ * (it may hold NaN or Inf) and it adds nothing to any gradient; a streaming pass costs about what the valid tokens
+ * cost.  In a clip whose tokens are all padded the softmax is uniform over all S tokens, as the reference computes
+ * it: every token counts in the embedding, and the key and query leaves get nothing from that clip (its logits are
+ * constants).  NULL paddings are exactly the unmasked call: the same kernels, the same bits.  The
+ * backward takes the paddings its forward took.  Workspace (vp_op_probe_workspace_bytes), stream and determinism are
+ * those of the unmasked calls. */
 typedef struct vp_probe_dims {
   int32_t model_dim;   /* D */
   int32_t num_heads;   /* H; dim_per_head dh = D / H */
@@ -447,6 +458,12 @@ int vp_op_probe_forward(const vp_probe_dims* dims, const vp_probe_params* params
 int vp_op_probe_backward(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens, int dtype,
                          int64_t B, int64_t S, const float* dlogits, const vp_probe_grads* grads, void* ws,
                          size_t ws_bytes, void* stream);
+int vp_op_probe_forward_masked(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens, int dtype,
+                               int64_t B, int64_t S, const float* paddings, float* logits, float* emb, void* ws,
+                               size_t ws_bytes, void* stream);
+int vp_op_probe_backward_masked(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens,
+                                int dtype, int64_t B, int64_t S, const float* paddings, const float* dlogits,
+                                const vp_probe_grads* grads, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------- gallery search: fused scores and top-k ----------------
  * The retrieval step of the LvT models: for each query, the k gallery rows with the largest dot product.  Exact and

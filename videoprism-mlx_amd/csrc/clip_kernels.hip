@@ -1,7 +1,8 @@
 // Kernels of the LvT video-text path besides attention.
 //
 // Contrastive pooler (AttenTokenPoolingLayer, layers.py:1044-1136; num_queries = 1, no logit
-// cap, per-dim scale on, paddings None).  Its single query is a parameter, so the projected
+// cap, per-dim scale on; paddings None in the models, given to the *_masked kernels by the
+// classifier head's training ops).  Its single query is a parameter, so the projected
 // and scaled query q~[h] (layers.py:502-527, :676-681) is a constant and the key projection
 // folds into it on the host:  logit[g,h,s] = x[g,s,:].U[h,:] + q~[h].bk[h], U[h] = Wk[:,h,:] q~[h].
 // The constant q~[h].bk[h] shifts every logit of a row equally and cancels in the softmax, so
@@ -30,6 +31,9 @@ namespace {
 struct StoreLogits {
   float* __restrict__ logits;
   __device__ __forceinline__ void operator()(int64_t, int64_t idx, float v) const { logits[idx] = v; }
+  // a padded token (layers.py:51-72): exp(kPadLogit - max) is exactly 0 beside a valid token, and a clip of padded
+  // tokens alone has max = kPadLogit and the uniform softmax, so pool_stats_kernel needs no mask
+  __device__ __forceinline__ void dead(int64_t, int64_t idx) const { logits[idx] = kPadLogit; }
 };
 
 template <int NJ>
@@ -43,6 +47,23 @@ __global__ __launch_bounds__(256) void pool_logits_mfma_kernel(const bf16_t* __r
                                                                int D, const bf16_t* __restrict__ Ut, int H,
                                                                float* __restrict__ logits) {
   pool_mfma_pass<false>(x, rows, S, D, Ut, H, StoreLogits{logits});
+}
+
+// the same passes under token paddings pad [G][S] (pool_stream.h, PadRows)
+template <int NJ>
+__global__ __launch_bounds__(256) void pool_logits_masked_kernel(const void* __restrict__ x, int in_bf16,
+                                                                 int64_t rows, int S, int D,
+                                                                 const float* __restrict__ U, int H,
+                                                                 const float* __restrict__ pad,
+                                                                 float* __restrict__ logits) {
+  pool_scalar_pass<NJ, false>(x, in_bf16, rows, S, D, U, H, StoreLogits{logits}, PadRows{pad});
+}
+
+__global__ __launch_bounds__(256) void pool_logits_mfma_masked_kernel(const bf16_t* __restrict__ x, int64_t rows,
+                                                                      int S, int D, const bf16_t* __restrict__ Ut,
+                                                                      int H, const float* __restrict__ pad,
+                                                                      float* __restrict__ logits) {
+  pool_mfma_pass<false>(x, rows, S, D, Ut, H, StoreLogits{logits}, PadRows{pad});
 }
 
 __global__ __launch_bounds__(256) void pool_stats_kernel(const float* __restrict__ logits, int S,
@@ -76,6 +97,15 @@ __global__ __launch_bounds__(128) void pool_wsum_kernel(const void* __restrict__
                                                         const float* __restrict__ stats, int C,
                                                         float* __restrict__ zpart) {
   pool_wsum_pass(x, in_bf16, S, D, H, C, FillSoftmax{logits, stats}, zpart);
+}
+
+// under token paddings: the dead rows (pool_stream.h, DeadRows) are neither loaded nor summed
+__global__ __launch_bounds__(128) void pool_wsum_masked_kernel(const void* __restrict__ x, int in_bf16, int S, int D,
+                                                               int H, const float* __restrict__ logits,
+                                                               const float* __restrict__ stats,
+                                                               const float* __restrict__ pad, int C,
+                                                               float* __restrict__ zpart) {
+  pool_wsum_pass(x, in_bf16, S, D, H, C, FillSoftmax{logits, stats}, zpart, DeadRows{pad, stats, H});
 }
 
 // out[g][e] = sum_{i < n} part[g][i][e] in index order
@@ -242,15 +272,22 @@ __global__ __launch_bounds__(256) void similarity_kernel(const float* __restrict
 }  // namespace
 
 hipError_t pool_logits(const void* x, int in_bf16, int64_t rows, int S, int D, const float* U, const bf16_t* Ut,
-                       int H, float* logits, hipStream_t s) {
+                       int H, float* logits, hipStream_t s, const float* pad) {
   if (D % 64 || D > kPoolMaxD || H < 1 || H > kPoolMaxH || rows % S) return hipErrorInvalidValue;
   if (in_bf16 && Ut && S % 32 == 0) {
     const int64_t grid = (rows / 32 + 3) / 4;
-    hipLaunchKernelGGL(pool_logits_mfma_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)x, rows, S,
-                       D, Ut, H, logits);
+    if (pad)
+      hipLaunchKernelGGL(pool_logits_mfma_masked_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)x,
+                         rows, S, D, Ut, H, pad, logits);
+    else
+      hipLaunchKernelGGL(pool_logits_mfma_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)x, rows, S,
+                         D, Ut, H, logits);
     return hipGetLastError();
   }
   const int64_t grid = (rows + kPlRows - 1) / kPlRows;
+  if (pad)
+    return launch_pool_scalar(&pool_logits_masked_kernel<16>, &pool_logits_masked_kernel<24>, dim3((unsigned)grid), D,
+                              H, s, x, in_bf16, rows, S, D, U, H, pad, logits);
   return launch_pool_scalar(&pool_logits_kernel<16>, &pool_logits_kernel<24>, dim3((unsigned)grid), D, H, s, x, in_bf16,
                             rows, S, D, U, H, logits);
 }
@@ -263,14 +300,18 @@ hipError_t pool_reduce(const float* part, int n, int64_t HD, int64_t groups, flo
 }
 
 hipError_t pool_softmax_wsum(const void* x, int in_bf16, int G, int S, int D, int H, const float* logits,
-                             float* stats, float* zpart, float* z, hipStream_t s) {
+                             float* stats, float* zpart, float* z, hipStream_t s, const float* pad) {
   if (D % 128 || D > kPoolMaxD || H < 1 || H > kPoolMaxH) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pool_stats_kernel, dim3(G * H), dim3(256), 0, s, logits, S, stats);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const int C = (S + kPwRows - 1) / kPwRows;
-  hipLaunchKernelGGL(pool_wsum_kernel, dim3(G * C * ((D + 255) / 256)), dim3(128), 0, s, x, in_bf16, S, D, H, logits, stats,
-                     C, zpart);
+  if (pad)
+    hipLaunchKernelGGL(pool_wsum_masked_kernel, dim3(G * C * ((D + 255) / 256)), dim3(128), 0, s, x, in_bf16, S, D, H,
+                       logits, stats, pad, C, zpart);
+  else
+    hipLaunchKernelGGL(pool_wsum_kernel, dim3(G * C * ((D + 255) / 256)), dim3(128), 0, s, x, in_bf16, S, D, H, logits, stats,
+                       C, zpart);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   return pool_reduce(zpart, C, (int64_t)H * D, G, z, s);

@@ -262,6 +262,9 @@ struct StoreDl {
   __device__ __forceinline__ void operator()(int64_t gh, int64_t idx, float dp) const {
     dl[idx] = softmax_p(logits, stats, gh, idx) * (dp - r[gh]);
   }
+  // a padded token's logit is the constant kPadLogit: nothing flows through it to U, whatever p is (exactly 0
+  // beside a valid token, 1 / S in a clip of padded tokens alone), and dp is never formed
+  __device__ __forceinline__ void dead(int64_t, int64_t idx) const { dl[idx] = 0.0f; }
 };
 
 // pool_stream.h pass 1 with the operand of the workgroup's (wave's) clip: dz [B][H][D], dzt [B][32][D]
@@ -282,6 +285,28 @@ __global__ __launch_bounds__(256) void probe_dl_mfma_kernel(const bf16_t* __rest
   pool_mfma_pass<true>(x, rows, S, D, dzt, H, StoreDl{logits, stats, r, dl});
 }
 
+// the same under token paddings pad [B][S]: every padded row is dead in the backward (pool_stream.h, PadRows)
+template <int NJ>
+__global__ __launch_bounds__(256) void probe_dl_masked_kernel(const void* __restrict__ x, int in_bf16, int S, int D,
+                                                              const float* __restrict__ dz, int H,
+                                                              const float* __restrict__ logits,
+                                                              const float* __restrict__ stats,
+                                                              const float* __restrict__ r,
+                                                              const float* __restrict__ pad,
+                                                              float* __restrict__ dl) {
+  pool_scalar_pass<NJ, true>(x, in_bf16, 0, S, D, dz, H, StoreDl{logits, stats, r, dl}, PadRows{pad});
+}
+
+__global__ __launch_bounds__(256) void probe_dl_mfma_masked_kernel(const bf16_t* __restrict__ x, int64_t rows, int S,
+                                                                   int D, const bf16_t* __restrict__ dzt, int H,
+                                                                   const float* __restrict__ logits,
+                                                                   const float* __restrict__ stats,
+                                                                   const float* __restrict__ r,
+                                                                   const float* __restrict__ pad,
+                                                                   float* __restrict__ dl) {
+  pool_mfma_pass<true>(x, rows, S, D, dzt, H, StoreDl{logits, stats, r, dl}, PadRows{pad});
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // pass 2: part[g][c][h][d] = sum over the rows of chunk c of dl[g,h,s] x[g*S+s][d]: pool_stream.h pass 2 with the
 // signed weights read as they are, the [256][16] weights visited by head (consecutive threads read consecutive s)
@@ -296,6 +321,14 @@ __global__ __launch_bounds__(128) void probe_wsum_kernel(const void* __restrict_
                                                          const float* __restrict__ dl, int C,
                                                          float* __restrict__ part) {
   pool_wsum_pass(x, in_bf16, S, D, H, C, FillDl{dl}, part);
+}
+
+// under token paddings: dl is exactly 0 at the padded rows, which are neither loaded nor summed
+__global__ __launch_bounds__(128) void probe_wsum_masked_kernel(const void* __restrict__ x, int in_bf16, int S, int D,
+                                                                int H, const float* __restrict__ dl,
+                                                                const float* __restrict__ pad, int C,
+                                                                float* __restrict__ part) {
+  pool_wsum_pass(x, in_bf16, S, D, H, C, FillDl{dl}, part, PadRows{pad});
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -401,25 +434,38 @@ hipError_t probe_dz_finish(const float* z, float* dz, int B, int H, int D, int s
 bool probe_dl_uses_mfma(int in_bf16, int S) { return in_bf16 && S % 32 == 0; }
 
 hipError_t probe_dl(const void* x, int in_bf16, int B, int S, int D, int H, const float* dz, const bf16_t* dzt,
-                    const float* logits, const float* stats, const float* r, float* dl, hipStream_t s) {
+                    const float* logits, const float* stats, const float* r, float* dl, hipStream_t s,
+                    const float* pad) {
   if (D % 64 || D > kPoolMaxD || H < 1 || H > kPoolMaxH || B < 1 || S < 1 || B > 65535) return hipErrorInvalidValue;
   if (probe_dl_uses_mfma(in_bf16, S) && dzt) {
     const int64_t rows = (int64_t)B * S;
     const int64_t grid = (rows / 32 + 3) / 4;
-    hipLaunchKernelGGL(probe_dl_mfma_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)x, rows, S, D, dzt,
-                       H, logits, stats, r, dl);
+    if (pad)
+      hipLaunchKernelGGL(probe_dl_mfma_masked_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)x, rows, S,
+                         D, dzt, H, logits, stats, r, pad, dl);
+    else
+      hipLaunchKernelGGL(probe_dl_mfma_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const bf16_t*)x, rows, S, D, dzt,
+                         H, logits, stats, r, dl);
     return hipGetLastError();
   }
+  if (pad)
+    return launch_pool_scalar(&probe_dl_masked_kernel<16>, &probe_dl_masked_kernel<24>,
+                              dim3((S + kPlRows - 1) / kPlRows, B), D, H, s, x, in_bf16, S, D, dz, H, logits, stats, r,
+                              pad, dl);
   return launch_pool_scalar(&probe_dl_kernel<16>, &probe_dl_kernel<24>, dim3((S + kPlRows - 1) / kPlRows, B), D, H, s, x,
                             in_bf16, S, D, dz, H, logits, stats, r, dl);
 }
 
 hipError_t probe_wsum(const void* x, int in_bf16, int B, int S, int D, int H, const float* dl, float* part,
-                      float* dUclip, float* dU, hipStream_t s) {
+                      float* dUclip, float* dU, hipStream_t s, const float* pad) {
   if (D % 128 || D > kPoolMaxD || H < 1 || H > kPoolMaxH || B < 1 || S < 1) return hipErrorInvalidValue;
   const int C = (S + kPwRows - 1) / kPwRows;
-  hipLaunchKernelGGL(probe_wsum_kernel, dim3(B * C * ((D + 255) / 256)), dim3(128), 0, s, x, in_bf16, S, D, H, dl, C,
-                     part);
+  if (pad)
+    hipLaunchKernelGGL(probe_wsum_masked_kernel, dim3(B * C * ((D + 255) / 256)), dim3(128), 0, s, x, in_bf16, S, D, H,
+                       dl, pad, C, part);
+  else
+    hipLaunchKernelGGL(probe_wsum_kernel, dim3(B * C * ((D + 255) / 256)), dim3(128), 0, s, x, in_bf16, S, D, H, dl, C,
+                       part);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // over the chunks of each clip, then over the clips: B times the workgroups of one sweep over all B * C partials

@@ -18,11 +18,11 @@ constexpr int kMaxTextLen = 1024;  // L + 1 (CLS) tokens; TEXT_MAX_LEN is 64 (mo
 namespace vpi {
 
 hipError_t pooler_stream(hipStream_t s, int bf, const PoolerW& pw, const void* feat, int G, int Sg, int D, int NH,
-                         const PoolScratch& sc) {
+                         const PoolScratch& sc, const float* pad) {
   const hipError_t e = vp::pool_logits(feat, bf, (int64_t)G * Sg, Sg, D, pw.U, bf ? (const vp::bf16_t*)pw.Ut : nullptr,
-                                       NH, sc.logits, s);
+                                       NH, sc.logits, s, pad);
   if (e != hipSuccess) return e;
-  return vp::pool_softmax_wsum(feat, bf, G, Sg, D, NH, sc.logits, sc.stats, sc.zpart, sc.z, s);
+  return vp::pool_softmax_wsum(feat, bf, G, Sg, D, NH, sc.logits, sc.stats, sc.zpart, sc.z, s, pad);
 }
 
 hipError_t pooler_project(hipStream_t s, const PoolerW& pw, int G, int D, int NH, const PoolScratch& sc, int do_l2,

@@ -382,9 +382,10 @@ inline PoolWs carve_pool_ws(size_t& off, int64_t rows, int64_t G, int64_t D, int
   return L;
 }
 
-// The two streaming passes over feat [G*Sg][D] (bf: bf16, else fp32): logits, softmax statistics, z (vp_clip.cpp)
+// The two streaming passes over feat [G*Sg][D] (bf: bf16, else fp32): logits, softmax statistics, z (vp_clip.cpp);
+// pad: token paddings [G][Sg] or null (vp_kernels.h, pool_logits)
 hipError_t pooler_stream(hipStream_t s, int bf, const PoolerW& pw, const void* feat, int G, int Sg, int D, int NH,
-                         const PoolScratch& sc);
+                         const PoolScratch& sc, const float* pad = nullptr);
 // ... then the value projection per head, the output projection over K = NH * dp (split 8 ways into zpart, free
 // again once z is summed, where that fills the device), LayerNorm and, if do_l2, L2 -> dst [G][D]
 hipError_t pooler_project(hipStream_t s, const PoolerW& pw, int G, int D, int NH, const PoolScratch& sc, int do_l2,

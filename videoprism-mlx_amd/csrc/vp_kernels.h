@@ -208,10 +208,13 @@ constexpr int kPoolMaxH = 16;  // most heads they take (a thread of the weighted
 // contrastive pooler: logits[g][h][s] = x[g*S+s] . U[h]; then softmax per (g,h) and
 // z[g][h][:] = sum_s p x (zpart scratch: [G][pool_chunks(S)][H][D], stats [G*H][2])
 // (bf16 x with Ut = [32][D] bf16 (U_hi | U_lo | 0) and S % 32 == 0: MFMA kernel)
+// pad: token paddings [G][S] fp32 (padded iff > 0.5; layers.py:1103-1106) or null: a padded token's logit is
+// -0.7 * FLT_MAX, and its row of x is not read unless every token of its clip is padded (pool_stream.h).  Null
+// launches the kernels that have no such parameter.
 hipError_t pool_logits(const void* x, int in_bf16, int64_t rows, int S, int D, const float* U, const bf16_t* Ut,
-                       int H, float* logits, hipStream_t s);
+                       int H, float* logits, hipStream_t s, const float* pad = nullptr);
 hipError_t pool_softmax_wsum(const void* x, int in_bf16, int G, int S, int D, int H, const float* logits,
-                             float* stats, float* zpart, float* z, hipStream_t s);
+                             float* stats, float* zpart, float* z, hipStream_t s, const float* pad = nullptr);
 int pool_chunks(int S);
 // out[g][e] = sum_{i < n} part[g][i][e] in index order, e < HD, g < groups (chunk sums of a weighted-sum pass)
 hipError_t pool_reduce(const float* part, int n, int64_t HD, int64_t groups, float* out, hipStream_t s);
@@ -259,12 +262,14 @@ hipError_t probe_ln_bwd(const float* x, const float* dy, const float* gamma, int
 hipError_t probe_dz_finish(const float* z, float* dz, int B, int H, int D, int split, bf16_t* dzt, float* r,
                            hipStream_t s);
 // pass 1: dl [B][H][S] = p (x . dz - r), p from the forward's logits and stats (bf16 x with S % 32 == 0 and dzt:
-// the MFMA kernel); pass 2: dU [H][D] = sum_{b,s} dl x through part [B][pool_chunks(S)][H][D] and dUclip [B][H][D]
+// the MFMA kernel); pass 2: dU [H][D] = sum_{b,s} dl x through part [B][pool_chunks(S)][H][D] and dUclip [B][H][D].
+// pad: the forward's token paddings [B][S] or null: dl is exactly 0 at a padded token and its row is never read
 bool probe_dl_uses_mfma(int in_bf16, int S);
 hipError_t probe_dl(const void* x, int in_bf16, int B, int S, int D, int H, const float* dz, const bf16_t* dzt,
-                    const float* logits, const float* stats, const float* r, float* dl, hipStream_t s);
+                    const float* logits, const float* stats, const float* r, float* dl, hipStream_t s,
+                    const float* pad = nullptr);
 hipError_t probe_wsum(const void* x, int in_bf16, int B, int S, int D, int H, const float* dl, float* part,
-                      float* dUclip, float* dU, hipStream_t s);
+                      float* dUclip, float* dU, hipStream_t s, const float* pad = nullptr);
 // dwk [D][H][dh] = dU[h][d] q~[h][j]
 hipError_t probe_fold_bwd(const float* dU, const float* qt, int D, int H, float* dwk, hipStream_t s);
 // dqraw [H][dh] = dq~ c softplus(pds), dpds [dh] = c sigmoid(pds) sum_h dq~ qraw

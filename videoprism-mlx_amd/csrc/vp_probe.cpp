@@ -1,7 +1,10 @@
 // C-ABI of the classifier head's training ops (vp_op_probe_*): forward and backward of atten_pooler + projection
 // (encoders.py:634-652) over frozen tokens.  The forward folds the query into the key projection on the device
 // (probe_kernels.hip) and then runs the engines' pooler forward (pooler_stream, pooler_project) and the projection;
-// the backward is steps 1-8 below, two streaming passes over the tokens and parameter-sized products.
+// the backward is steps 1-8 below, two streaming passes over the tokens and parameter-sized products.  The
+// *_masked entry points take token paddings [B][S] as well (pool_stream.h says what the passes do with them); the
+// unmasked ones are their paddings = NULL case, which launches the kernels without the parameter.  The mask needs no
+// workspace of its own.
 #include "vp_internal.h"
 
 using namespace vpi;
@@ -92,6 +95,12 @@ int vp_op_probe_workspace_bytes(const vp_probe_dims* dims, int64_t B, int64_t S,
 
 int vp_op_probe_forward(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens, int dtype,
                         int64_t B, int64_t S, float* logits, float* emb, void* ws, size_t ws_bytes, void* stream) {
+  return vp_op_probe_forward_masked(dims, params, tokens, dtype, B, S, nullptr, logits, emb, ws, ws_bytes, stream);
+}
+
+int vp_op_probe_forward_masked(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens, int dtype,
+                               int64_t B, int64_t S, const float* paddings, float* logits, float* emb, void* ws,
+                               size_t ws_bytes, void* stream) {
   using namespace vp;
   if (!dims || !params || !tokens || !logits || !ws || any_null(*params)) return fail(VP_EINVAL, "null argument");
   ProbeWs L;
@@ -110,7 +119,7 @@ int vp_op_probe_forward(const vp_probe_dims* dims, const vp_probe_params* params
   // the pooler's forward on the folded weights, then the projection
   const PoolerW pw{Ut, f32(L.U), f32(L.wvt), p.value_b, f32(L.wpt), p.post_b, f32(L.gamma), p.ln_bias, dh};
   const PoolScratch sc = L.fw.at(ws);
-  VP_HIP(pooler_stream(s, bf, pw, tokens, G, (int)S, D, H, sc));
+  VP_HIP(pooler_stream(s, bf, pw, tokens, G, (int)S, D, H, sc, paddings));
   VP_HIP(pooler_project(s, pw, G, D, H, sc, 0, f32(L.emb)));
   VP_HIP(small_gemm(f32(L.emb), D, 0, p.proj_kernel, 0, p.proj_bias, 0, logits, C, 0, G, C, D, 1, s));
   if (emb) VP_HIP(hipMemcpyAsync(emb, f32(L.emb), (size_t)B * D * 4, hipMemcpyDeviceToDevice, s));
@@ -120,6 +129,12 @@ int vp_op_probe_forward(const vp_probe_dims* dims, const vp_probe_params* params
 int vp_op_probe_backward(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens, int dtype,
                          int64_t B, int64_t S, const float* dlogits, const vp_probe_grads* grads, void* ws,
                          size_t ws_bytes, void* stream) {
+  return vp_op_probe_backward_masked(dims, params, tokens, dtype, B, S, nullptr, dlogits, grads, ws, ws_bytes, stream);
+}
+
+int vp_op_probe_backward_masked(const vp_probe_dims* dims, const vp_probe_params* params, const void* tokens,
+                                int dtype, int64_t B, int64_t S, const float* paddings, const float* dlogits,
+                                const vp_probe_grads* grads, void* ws, size_t ws_bytes, void* stream) {
   using namespace vp;
   if (!dims || !params || !tokens || !dlogits || !grads || !ws || any_null(*params) || any_null(*grads))
     return fail(VP_EINVAL, "null argument");
@@ -153,9 +168,9 @@ int vp_op_probe_backward(const vp_probe_dims* dims, const vp_probe_params* param
   // 5. r = z . dz (the softmax term needs no pass) and, for bf16 tokens, the hi | lo operand of each clip; pass 1
   VP_HIP(probe_dz_finish(f32(L.fw.z), f32(L.dz), G, H, D, bf, dzt, f32(L.r), s));
   VP_HIP(probe_dl(tokens, bf, G, (int)S, D, H, f32(L.dz), bf ? dzt : nullptr, f32(L.fw.logits), f32(L.fw.stats), f32(L.r),
-                  f32(L.dl), s));
+                  f32(L.dl), s, paddings));
   // 6. pass 2
-  VP_HIP(probe_wsum(tokens, bf, G, (int)S, D, H, f32(L.dl), f32(L.fw.zpart), f32(L.dUclip), f32(L.dU), s));
+  VP_HIP(probe_wsum(tokens, bf, G, (int)S, D, H, f32(L.dl), f32(L.fw.zpart), f32(L.dUclip), f32(L.dU), s, paddings));
   // 7. fold: dWk = dU (x) q~, dq~[h] = Wk[:,h,:]^T dU[h], dbk = 0
   VP_HIP(probe_fold_bwd(f32(L.dU), f32(L.qt), D, H, g.key_w, s));
   VP_HIP(hipMemsetAsync(g.key_b, 0, (size_t)D * 4, s));

@@ -211,6 +211,12 @@ _SIGNATURES = {
                                     c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vp_op_probe_backward": (c_int, [POINTER(vp_probe_dims), POINTER(vp_probe_params), c_void_p, c_int, c_int64,
                                      c_int64, c_void_p, POINTER(vp_probe_params), c_void_p, c_size_t, c_void_p]),
+    # ... under token paddings [B, S] (device fp32, after S; NULL: the calls above)
+    "vp_op_probe_forward_masked": (c_int, [POINTER(vp_probe_dims), POINTER(vp_probe_params), c_void_p, c_int, c_int64,
+                                           c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_op_probe_backward_masked": (c_int, [POINTER(vp_probe_dims), POINTER(vp_probe_params), c_void_p, c_int, c_int64,
+                                            c_int64, c_void_p, c_void_p, POINTER(vp_probe_params), c_void_p, c_size_t,
+                                            c_void_p]),
     # gallery search: fused scores and top-k (videoprism/retrieval.py)
     "vp_op_topk_workspace_bytes": (c_int, [c_int64, c_int64, POINTER(c_size_t)]),
     "vp_op_topk": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
@@ -584,26 +590,43 @@ def op_probe_workspace_bytes(model_dim, num_heads, num_classes, B, S) -> int:
     return n.value
 
 
-def op_probe_forward(dims, tensors, tokens, logits, emb, ws, ws_bytes=None, stream=None):
+def _probe_paddings(entry, paddings, tokens):
+    """(entry point, its paddings arguments): the *_masked call for token paddings (a contiguous fp32 [B, S] tensor
+    on the tokens' device), the unmasked one for None."""
+    if paddings is None:
+        return entry, ()
+    import torch
+    if (paddings.dtype != torch.float32 or not paddings.is_contiguous() or paddings.device != tokens.device or
+            tuple(paddings.shape) != tuple(tokens.shape[:2])):
+        raise ValueError(f"paddings must be a contiguous fp32 {tuple(tokens.shape[:2])} tensor on {tokens.device}")
+    return entry + "_masked", (_ptr(paddings),)
+
+
+def op_probe_forward(dims, tensors, tokens, logits, emb, ws, ws_bytes=None, stream=None, paddings=None):
     """logits [B, C] (and emb [B, D] unless None) of the head over tokens [B, S, D]; fills the workspace `ws`
-    (uint8, op_probe_workspace_bytes) with what op_probe_backward needs."""
+    (uint8, op_probe_workspace_bytes) with what op_probe_backward needs.  paddings: None, or fp32 [B, S] with
+    > 0.5 at the padded tokens (vp_op_probe_forward_masked)."""
     import torch
     B, S, _ = tokens.shape
     d = vp_probe_dims(*dims)
+    entry, pad = _probe_paddings("vp_op_probe_forward", paddings, tokens)
     with torch.cuda.device(tokens.device):  # no handle: the ops launch on the current device
-        call("vp_op_probe_forward", ctypes.byref(d), ctypes.byref(_probe_struct(tensors)), _ptr(tokens), _prec(tokens),
-             B, S, _ptr(logits), _ptr(emb), _ptr(ws), ws.numel() if ws_bytes is None else ws_bytes, _stream(stream))
+        call(entry, ctypes.byref(d), ctypes.byref(_probe_struct(tensors)), _ptr(tokens), _prec(tokens),
+             B, S, *pad, _ptr(logits), _ptr(emb), _ptr(ws), ws.numel() if ws_bytes is None else ws_bytes,
+             _stream(stream))
     return logits
 
 
-def op_probe_backward(dims, tensors, tokens, dlogits, grads, ws, ws_bytes=None, stream=None):
-    """Fills `grads` (same members as `tensors`) from dlogits [B, C] and the workspace the forward filled."""
+def op_probe_backward(dims, tensors, tokens, dlogits, grads, ws, ws_bytes=None, stream=None, paddings=None):
+    """Fills `grads` (same members as `tensors`) from dlogits [B, C] and the workspace the forward filled;
+    paddings: what that forward was given."""
     import torch
     B, S, _ = tokens.shape
     d = vp_probe_dims(*dims)
+    entry, pad = _probe_paddings("vp_op_probe_backward", paddings, tokens)
     with torch.cuda.device(tokens.device):
-        call("vp_op_probe_backward", ctypes.byref(d), ctypes.byref(_probe_struct(tensors)), _ptr(tokens),
-             _prec(tokens), B, S, _ptr(dlogits), ctypes.byref(_probe_struct(grads)), _ptr(ws),
+        call(entry, ctypes.byref(d), ctypes.byref(_probe_struct(tensors)), _ptr(tokens),
+             _prec(tokens), B, S, *pad, _ptr(dlogits), ctypes.byref(_probe_struct(grads)), _ptr(ws),
              ws.numel() if ws_bytes is None else ws_bytes, _stream(stream))
     return grads
 
