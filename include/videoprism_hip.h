@@ -511,6 +511,40 @@ int vp_op_topk_groups_merge(const float* scores_in, const int64_t* groups_in, co
                             int64_t Q, int64_t k_in, int64_t k, float* scores, int64_t* groups, int64_t* ids,
                             void* stream);
 
+/* ---------------- masked gallery search: a subset of the rows, and deleted rows ----------------
+ * One bit per gallery row decides, inside the scan, whether the row may enter a query's list: the two searches above
+ * over the allowed rows only.  The mask is packed bits in device uint32 words, 4-byte aligned: row r is allowed where
+ * bit r & 31 of word r >> 5 is set.  A mask is ceil(N / 32) words; the spare bits of its last word are ignored
+ * whatever they hold and nothing past those words is read.
+ *   mask, mask_query_stride_words   stride 0: one mask [ceil(N / 32)] for all queries.  Otherwise query q's mask
+ *            starts at word q * stride (stride >= ceil(N / 32)): each query searches its own subset.
+ * The result is the best k of the allowed rows (groups: of the groups that have an allowed row, each with its best
+ * allowed row), in the order and with the padding of the unmasked calls.  An allowed row's score has the bits the
+ * unmasked search gives it, so the call returns what vp_op_topk / vp_op_topk_groups return on a gallery that holds the
+ * allowed rows alone, ids mapped back, and masked shard lists merge with vp_op_topk_merge / vp_op_topk_groups_merge
+ * to the bits of the whole gallery's masked search.  Rows that are not allowed may or may not be read; what they hold
+ * (NaN, inf) does not matter.  Groups of 64 rows that no query of a workgroup allows cost neither loads nor MFMAs,
+ * and the 512-row tiles are dealt to the workgroups in turn, so long runs of such rows shorten the whole search.
+ * N < 2^32 - 1.  Everything else is the unmasked call's: limits, dtypes, alignment, stateless, asynchronous on `stream` with no
+ * synchronisation and no launch elsewhere, Q == 0 launches nothing, N == 0 gives all padding (the mask may then be
+ * null).  A null mask with N > 0 is VP_EINVAL: the unmasked call is the one for that.
+ *   ws       the unmasked call's: vp_op_topk_workspace_bytes(Q, k) for vp_op_topk_masked,
+ *            vp_op_topk_groups_workspace_bytes(Q, k) for vp_op_topk_groups_masked
+ * vp_op_rowmask_pack: the words from one byte per row.  allow is device uint8 (or bool) [Q, N], contiguous, nonzero =
+ * allowed; out[q * stride + w] (stride >= ceil(N / 32) words) gets the bits of rows 32 w .. 32 w + 31 of allow[q], zero
+ * past N, ANDed with and_words[q * and_stride + w] where and_words is not null (and_stride 0: the same packed mask
+ * for every q; else >= ceil(N / 32)): a caller's filter and a mask of rows not deleted combine in the one call.  Only
+ * words that hold a row are written.  Q == 0 or N == 0 launches nothing. */
+int vp_op_rowmask_pack(const uint8_t* allow, int64_t Q, int64_t N, const uint32_t* and_words, int64_t and_stride,
+                       uint32_t* out_words, int64_t stride, void* stream);
+int vp_op_topk_masked(const float* queries, int64_t Q, const void* gallery, int gallery_dtype, int64_t N, int64_t ld,
+                      int64_t D, int64_t k, int64_t id_base, const uint32_t* mask, int64_t mask_query_stride_words,
+                      float* scores, int64_t* ids, void* ws, size_t ws_bytes, void* stream);
+int vp_op_topk_groups_masked(const float* queries, int64_t Q, const void* gallery, int gallery_dtype, int64_t N,
+                             int64_t ld, int64_t D, const int64_t* labels, int64_t k, int64_t id_base,
+                             const uint32_t* mask, int64_t mask_query_stride_words, float* scores, int64_t* groups,
+                             int64_t* ids, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------- multi-GPU: RCCL all-gather of pooled clip embeddings ----------------
  * The reference runs on one device; its video-text usage scores every clip against every query,
  * `similarities = video_emb @ text_emb.T` (README.md:81, verify_clip_models.py:84).  With clips

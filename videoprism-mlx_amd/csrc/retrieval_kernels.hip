@@ -40,6 +40,21 @@
 // beat it, so the list is the best k groups of the rows seen, each with its best row (of equal scores the first).
 // The labels of a lane's candidates in a tile are read together, and of candidates that follow one another in a lane
 // with the same label only the best keeps its turn (tk_insert).
+//
+// The masked search (vp_op_topk_masked / vp_op_topk_groups_masked; DESIGN.md §4 "Masked search") is
+// topk_scan_kernel<BF16, GROUPED, true>, again the same text.  The mask is packed bits, bit r & 31 of word r >> 5 set
+// where row r is allowed; a 32-row MFMA tile is one word and a wave's 64 rows are two, read one tile ahead.  One mask
+// serves all queries (stride 0: every lane reads the same two words) or each query has its own (lane l reads query
+// l & 31's).  After the MFMAs and before the pre-check a lane sets the accumulators of rows its query does not allow
+// to -inf, which no comparison of the selection passes; the instructions that form a score are the unmasked ones, so
+// an allowed row's score has the unmasked search's bits and the lists are those of a gallery of the allowed rows
+// alone.  A wave none of whose queries allows any of its 64 rows skips the tile's loads and MFMAs; under the shared
+// mask a row that is not allowed is not loaded either.  So that such savings shorten the search and not only some
+// workgroups' share of it, the masked scan deals the 512-row tiles to the workgroups in turn (workgroup x of P takes
+// tiles x, x + P, ...) where the unmasked one gives each a contiguous range: a workgroup's rows still ascend, and the
+// merge does not care how the rows were split.  Bits of rows past N are never looked at (every use of a score
+// is behind `row < p1`) and no word past ceil(N / 32) per mask is read.  rowmask_pack_kernel makes the words from one
+// byte per row, a ballot per 64 rows.
 #include "vp_common.h"
 #include "vp_kernels.h"
 
@@ -231,13 +246,23 @@ __device__ __forceinline__ void tk_insert(const f32x16 (&acc)[2], int64_t r0, in
   }
 }
 
-template <bool BF16, bool GROUPED>
+// the two mask words of the wave's rows r0 .. r0 + 63 (r0 a multiple of 64); a word whose rows all lie past the range
+// is not read, and lanes without a query hold zeros
+__device__ __forceinline__ void tk_mask_load(uint32_t (&m)[2], const uint32_t* mq, bool mlane, int64_t r0, int64_t p1) {
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt) m[rt] = mlane && r0 + 32 * rt < p1 ? mq[(r0 >> 5) + rt] : 0u;
+}
+
+// MASKED: a row enters a list only where its bit of `mask` is set (see the file comment); the other instantiations do
+// not look at the two arguments.
+template <bool BF16, bool GROUPED, bool MASKED>
 __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __restrict__ queries, int64_t Q,
                                                         const void* __restrict__ gallery, int64_t N, int64_t ld, int D,
                                                         int k, int G, int64_t rows_per_part, int64_t id_base,
                                                         float* __restrict__ ws_sc, int64_t* __restrict__ ws_id,
                                                         const int64_t* __restrict__ labels,
-                                                        int64_t* __restrict__ ws_gr) {
+                                                        int64_t* __restrict__ ws_gr,
+                                                        const uint32_t* __restrict__ mask, int64_t mask_stride) {
   extern __shared__ __attribute__((aligned(16))) char tk_smem[];
   f32x4* bq = reinterpret_cast<f32x4*>(tk_smem);                          // D * G * 4 bytes, fragment order
   float* lsc = reinterpret_cast<float*>(tk_smem + (size_t)D * G * 4);     // [G][k]
@@ -281,22 +306,51 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
   }
   __syncthreads();
 
-  const int64_t p0 = (int64_t)blockIdx.x * rows_per_part;
-  const int64_t p1 = p0 + rows_per_part < N ? p0 + rows_per_part : N;
+  // the workgroup's rows: [p0, p1), tile after tile.  MASKED: the tiles are dealt to the workgroups in turn instead
+  // (workgroup x takes tiles x, x + gridDim.x, ... to the gallery's end: rows_per_part is then the step, gridDim.x
+  // tiles), so a long run of rows that are not allowed shortens every workgroup's walk a little and no workgroup's
+  // not at all; the rows still ascend, and the lists count them from the workgroup's first tile
+  const int64_t p0 = (int64_t)blockIdx.x * (MASKED ? (int64_t)kTkRows : rows_per_part);
+  const int64_t p1 = MASKED ? N : p0 + rows_per_part < N ? p0 + rows_per_part : N;
+  const int tstep = MASKED ? (int)rows_per_part : kTkRows;  // at most kTopkMaxParts tiles
   const int64_t row_bytes = ld * (BF16 ? 2 : 4);
   const int nt = (D * (BF16 ? 2 : 4)) >> 5;  // 32-byte steps of a row: a multiple of 4
   const bool qlane = i < G;
+  // MASKED: the lane's mask (its query's, or the shared one in every lane) and the words of the wave's 64 rows of the
+  // tile to come, two 32-row words read one tile ahead; a tile starts at a multiple of 512, so r0 is one of 64
+  const uint32_t* mq = nullptr;
+  bool mlane = false, mshared = false;
+  uint32_t mnext[2] = {0u, 0u};
+  if constexpr (MASKED) {
+    mshared = mask_stride == 0;
+    mlane = mshared || (qlane && q0 + i < Q);
+    mq = mask + (mlane ? (q0 + i) * mask_stride : 0);
+    tk_mask_load(mnext, mq, mlane, p0 + 64 * w, p1);
+  }
   int par = 0;
-  for (int64_t tb = p0; tb < p1; tb += kTkRows, par ^= 1) {
+  for (int64_t tb = p0; tb < p1; tb += tstep, par ^= 1) {
     const int64_t r0 = tb + 64 * w;
     f32x16 acc[2] = {};
-    if (r0 < p1) {  // whole wave
+    uint32_t mw[2] = {mnext[0], mnext[1]};
+    bool wave = r0 < p1;
+    bool need[2] = {true, true};  // the lane's row of each 32-row tile is read
+    if constexpr (MASKED) {
+      if (tb + tstep < p1) tk_mask_load(mnext, mq, mlane, r0 + tstep, p1);
+      // no query of the wave allows any of its 64 rows: neither loads nor MFMAs (the branch is the wave's; the loads
+      // of a tile are all issued inside it, so a skipped tile leaves none in flight).  Under the shared mask every
+      // lane holds the rows' own bits and a row that is not allowed is not read either; per query, a 32-row tile
+      // that no query allows is not read
+      wave = wave && __ballot((mw[0] | mw[1]) != 0) != 0;
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) need[rt] = mshared ? (mw[rt] >> i) & 1 : __ballot(mw[rt] != 0) != 0;
+    }
+    if (wave) {  // whole wave
       const char* rp[2];
       bool ok[2];
 #pragma unroll
       for (int rt = 0; rt < 2; ++rt) {
         const int64_t row = r0 + 32 * rt + i;
-        ok[rt] = row < p1;
+        ok[rt] = row < p1 && need[rt];
         rp[rt] = static_cast<const char*>(gallery) + row * row_bytes + 16 * half;
       }
       f32x4 a0[2][4], a1[2][4];
@@ -309,6 +363,17 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
           if (t + 8 < nt) tk_load(a0, rp, ok, t + 8);
           tk_mma<BF16>(a1, bq, t + 4, G, i, half, qlane, acc);
         }
+      }
+    }
+    if constexpr (MASKED) {
+      // a row that the lane's query does not allow scores -inf from here on: it fails the pre-check and every
+      // comparison of tk_insert; an allowed row's score is what the MFMAs left
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        const uint32_t mh = mw[rt] >> (4 * half);
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+          if (!((mh >> ((q & 3) + 8 * (q >> 2))) & 1)) acc[rt][q] = -INFINITY;
       }
     }
     // lists last changed before the previous tile's final barrier
@@ -530,6 +595,31 @@ __global__ __launch_bounds__(256) void topk_groups_merge_kernel(const float* __r
   }
 }
 
+// The row mask of the masked search from one byte per row (vp_op_rowmask_pack): a wave takes 64 rows of one mask, a
+// lane reads its row's byte, the ballot of `nonzero` is the two words, and lanes 0 and 1 store one each, after the AND
+// with the same word of `andw` where that is given (and_stride 0: one such mask for all Q).  Rows past N give zero
+// bits; a word is written only where it holds a row, and every word that does is written by exactly one lane.
+constexpr int kPackRows = 256;  // rows of a workgroup: 4 waves
+
+__global__ __launch_bounds__(kPackRows) void rowmask_pack_kernel(const uint8_t* __restrict__ allow, int64_t Q, int64_t N,
+                                                                 const uint32_t* __restrict__ andw, int64_t and_stride,
+                                                                 uint32_t* __restrict__ out, int64_t stride) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r0 = (int64_t)blockIdx.x * kPackRows + (threadIdx.x & ~63);  // the wave's first row
+  if (r0 >= N) return;
+  for (int64_t q = blockIdx.y; q < Q; q += gridDim.y) {
+    const int64_t row = r0 + lane;
+    const bool on = row < N && allow[q * N + row] != 0;
+    const uint64_t b = __ballot(on);
+    const int64_t wd = (r0 >> 5) + lane;  // lanes 0 and 1: the word this lane stores
+    if (lane < 2 && r0 + 32 * lane < N) {
+      uint32_t v = (uint32_t)(b >> (32 * lane));
+      if (andw) v &= andw[q * and_stride + wd];
+      out[q * stride + wd] = v;
+    }
+  }
+}
+
 }  // namespace
 
 int topk_group(int D, int k) {
@@ -543,12 +633,14 @@ int topk_groups_group(int D, int k) {
 
 namespace {
 
-// both searches: labels == nullptr is the ungrouped one (ws_gr unused)
-template <bool GROUPED>
+// both searches: labels == nullptr is the ungrouped one (ws_gr unused); MASKED: mask / mask_stride as the kernel's
+template <bool GROUPED, bool MASKED>
 hipError_t topk_scan_launch(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
                             int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id, int64_t* ws_gr,
-                            int* parts_out, hipStream_t s) {
+                            const uint32_t* mask, int64_t mask_stride, int* parts_out, hipStream_t s) {
   if (Q < 1 || N < 0 || D < 64 || D % 64 || D > kPoolMaxD || k < 1 || k > kTopkMaxK || ld < D) return hipErrorInvalidValue;
+  if (MASKED && ((!mask && N > 0) || mask_stride < 0 || (mask_stride > 0 && mask_stride < (N + 31) / 32)))
+    return hipErrorInvalidValue;
   const int G = GROUPED ? topk_groups_group(D, k) : topk_group(D, k);
   const int64_t groups = (Q + G - 1) / G;
   if (groups > 65535) return hipErrorInvalidValue;
@@ -557,21 +649,28 @@ hipError_t topk_scan_launch(const float* queries, int64_t Q, const void* gallery
   int64_t parts = device_cu_count() / groups;
   parts = parts < 1 ? 1 : parts > kTopkMaxParts ? kTopkMaxParts : parts;
   parts = tiles < 1 ? 1 : parts > tiles ? tiles : parts;
-  const int64_t rows_per_part = tiles < 1 ? kTkRows : (tiles + parts - 1) / parts * kTkRows;
-  if (rows_per_part >= (int64_t)kTkNoRow) return hipErrorInvalidValue;
-  parts = tiles < 1 ? 1 : (N + rows_per_part - 1) / rows_per_part;
+  int64_t rows_per_part = tiles < 1 ? kTkRows : (tiles + parts - 1) / parts * kTkRows;
+  if (MASKED) {
+    // the tiles go to the workgroups in turn (see the kernel): the kernel's rows_per_part is the step from one of a
+    // workgroup's tiles to its next, and a list counts rows from the workgroup's first tile to the gallery's end
+    rows_per_part = parts * kTkRows;
+    if (N >= (int64_t)kTkNoRow) return hipErrorInvalidValue;
+  } else {
+    if (rows_per_part >= (int64_t)kTkNoRow) return hipErrorInvalidValue;
+    parts = tiles < 1 ? 1 : (N + rows_per_part - 1) / rows_per_part;
+  }
   const int lds = D * G * 4 + G * k * (GROUPED ? 16 : 8) + 2 * kTkWaves * 4;
-  const void* fn = bf16 ? reinterpret_cast<const void*>(&topk_scan_kernel<true, GROUPED>)
-                        : reinterpret_cast<const void*>(&topk_scan_kernel<false, GROUPED>);
+  const void* fn = bf16 ? reinterpret_cast<const void*>(&topk_scan_kernel<true, GROUPED, MASKED>)
+                        : reinterpret_cast<const void*>(&topk_scan_kernel<false, GROUPED, MASKED>);
   hipError_t e = ensure_dyn_lds(fn, kTkLdsBytes);
   if (e != hipSuccess) return e;
   const dim3 grid((unsigned)parts, (unsigned)groups);
   if (bf16)
-    hipLaunchKernelGGL((topk_scan_kernel<true, GROUPED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N, ld, D,
-                       k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr);
+    hipLaunchKernelGGL((topk_scan_kernel<true, GROUPED, MASKED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N,
+                       ld, D, k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr, mask, mask_stride);
   else
-    hipLaunchKernelGGL((topk_scan_kernel<false, GROUPED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N, ld, D,
-                       k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr);
+    hipLaunchKernelGGL((topk_scan_kernel<false, GROUPED, MASKED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery,
+                       N, ld, D, k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr, mask, mask_stride);
   *parts_out = (int)parts;
   return hipGetLastError();
 }
@@ -580,16 +679,45 @@ hipError_t topk_scan_launch(const float* queries, int64_t Q, const void* gallery
 
 hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D, int k,
                      int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s) {
-  return topk_scan_launch<false>(queries, Q, gallery, bf16, N, ld, D, k, nullptr, id_base, ws_sc, ws_id, nullptr,
-                                 parts_out, s);
+  return topk_scan_launch<false, false>(queries, Q, gallery, bf16, N, ld, D, k, nullptr, id_base, ws_sc, ws_id, nullptr,
+                                        nullptr, 0, parts_out, s);
 }
 
 hipError_t topk_groups_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
                             int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id, int64_t* ws_gr,
                             int* parts_out, hipStream_t s) {
   if (!labels && N > 0) return hipErrorInvalidValue;
-  return topk_scan_launch<true>(queries, Q, gallery, bf16, N, ld, D, k, labels, id_base, ws_sc, ws_id, ws_gr, parts_out,
-                                s);
+  return topk_scan_launch<true, false>(queries, Q, gallery, bf16, N, ld, D, k, labels, id_base, ws_sc, ws_id, ws_gr,
+                                       nullptr, 0, parts_out, s);
+}
+
+hipError_t topk_scan_masked(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
+                            int k, int64_t id_base, const uint32_t* mask, int64_t mask_stride, float* ws_sc,
+                            int64_t* ws_id, int* parts_out, hipStream_t s) {
+  return topk_scan_launch<false, true>(queries, Q, gallery, bf16, N, ld, D, k, nullptr, id_base, ws_sc, ws_id, nullptr,
+                                       mask, mask_stride, parts_out, s);
+}
+
+hipError_t topk_groups_scan_masked(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld,
+                                   int D, int k, const int64_t* labels, int64_t id_base, const uint32_t* mask,
+                                   int64_t mask_stride, float* ws_sc, int64_t* ws_id, int64_t* ws_gr, int* parts_out,
+                                   hipStream_t s) {
+  if (!labels && N > 0) return hipErrorInvalidValue;
+  return topk_scan_launch<true, true>(queries, Q, gallery, bf16, N, ld, D, k, labels, id_base, ws_sc, ws_id, ws_gr, mask,
+                                      mask_stride, parts_out, s);
+}
+
+hipError_t rowmask_pack(const uint8_t* allow, int64_t Q, int64_t N, const uint32_t* and_words, int64_t and_stride,
+                        uint32_t* out, int64_t stride, hipStream_t s) {
+  const int64_t words = (N + 31) / 32;
+  if (Q < 0 || N < 0 || !allow || !out || stride < words || and_stride < 0 || (and_stride > 0 && and_stride < words))
+    return hipErrorInvalidValue;
+  if (Q == 0 || N == 0) return hipSuccess;
+  const int64_t bx = (N + kPackRows - 1) / kPackRows;
+  if (bx > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rowmask_pack_kernel, dim3((unsigned)bx, (unsigned)(Q < 65535 ? Q : 65535)), dim3(kPackRows), 0, s,
+                     allow, Q, N, and_words, and_stride, out, stride);
+  return hipGetLastError();
 }
 
 hipError_t topk_merge(const float* sin, const int64_t* iin, int64_t parts, int64_t Q, int k_in, int k, float* so,

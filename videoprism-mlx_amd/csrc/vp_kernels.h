@@ -301,6 +301,21 @@ hipError_t topk_groups_scan(const float* queries, int64_t Q, const void* gallery
 // function of the set of (score, group, id) alone
 hipError_t topk_groups_merge(const float* sin, const int64_t* gin, const int64_t* iin, int64_t parts, int64_t Q, int k_in,
                              int k, float* so, int64_t* go, int64_t* io, hipStream_t s);
+// the masked search (DESIGN.md §4 "Masked search"): the two scans above over the rows whose bit of `mask` is set (bit
+// r & 31 of word r >> 5; ceil(N / 32) words a mask, bits past N ignored).  mask_stride 0: one mask for all queries;
+// else query q's mask starts at word q * mask_stride (>= ceil(N / 32)).  Lists, scores of allowed rows and the merges
+// are the unmasked ones'; N = 0 takes a null mask
+hipError_t topk_scan_masked(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
+                            int k, int64_t id_base, const uint32_t* mask, int64_t mask_stride, float* ws_sc,
+                            int64_t* ws_id, int* parts_out, hipStream_t s);
+hipError_t topk_groups_scan_masked(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld,
+                                   int D, int k, const int64_t* labels, int64_t id_base, const uint32_t* mask,
+                                   int64_t mask_stride, float* ws_sc, int64_t* ws_id, int64_t* ws_gr, int* parts_out,
+                                   hipStream_t s);
+// out[q * stride + w] = the packed bits of allow[q][32 w ..] != 0 (uint8 [Q][N], rows past N zero), ANDed with
+// and_words[q * and_stride + w] where and_words is given (and_stride 0: the same words for every q)
+hipError_t rowmask_pack(const uint8_t* allow, int64_t Q, int64_t N, const uint32_t* and_words, int64_t and_stride,
+                        uint32_t* out, int64_t stride, hipStream_t s);
 
 // ---- frame ingest (preprocess.hip) ----
 // video_utils.py:109-124: size of the resized frame and the crop window's origin in it (mode 0 centre

@@ -1,5 +1,6 @@
-// C-ABI of the gallery search (vp_op_topk*): argument checks, the workspace layout and the two passes of
-// retrieval_kernels.hip (per-range candidate lists, then their merge).
+// C-ABI of the gallery search (vp_op_topk*, vp_op_rowmask_pack): argument checks, the workspace layout and the two
+// passes of retrieval_kernels.hip (per-range candidate lists, then their merge).  The masked calls share the unmasked
+// ones' checks, workspace and merge; only the scan differs.
 #include "vp_internal.h"
 
 using namespace vpi;
@@ -44,6 +45,107 @@ int check_topk_k(int64_t Q, int64_t k, const char* op = "topk") {
 
 bool misaligned(const void* p) { return reinterpret_cast<uintptr_t>(p) & 15; }
 
+// the masked calls' two arguments: a mask wherever there are rows, 4-byte aligned; stride 0 (one mask for all queries)
+// or at least a mask's words
+int check_mask(const std::string& o, const uint32_t* mask, int64_t mask_stride, int64_t N) {
+  if (!mask && N != 0) return fail(VP_EINVAL, o + "null mask (the unmasked call searches every row)");
+  if (reinterpret_cast<uintptr_t>(mask) & 3) return fail(VP_EINVAL, o + "mask must be 4-byte aligned");
+  if (mask_stride < 0 || (mask_stride > 0 && mask_stride < (N + 31) / 32))
+    return fail(VP_EINVAL, o + "mask_query_stride_words must be 0 or >= ceil(N / 32)");
+  // a list of the masked scan counts rows from its first tile to the gallery's end, in 32 bits
+  if (N >= (int64_t)0xffffffff) return fail(VP_ENOTSUP, o + "N must be < 2^32 - 1");
+  return VP_OK;
+}
+
+// vp_op_topk (masked false: mask and mask_stride unused) and vp_op_topk_masked; `op` names the call in messages
+int topk_call(const char* op, bool masked, const float* queries, int64_t Q, const void* gallery, int gallery_dtype,
+              int64_t N, int64_t ld, int64_t D, int64_t k, int64_t id_base, const uint32_t* mask, int64_t mask_stride,
+              float* scores, int64_t* ids, void* ws, size_t ws_bytes, void* stream) {
+  const std::string o = std::string(op) + ": ";
+  if (!queries) return fail(VP_EINVAL, o + "null queries");
+  if (!gallery && N != 0) return fail(VP_EINVAL, o + "null gallery");
+  if (!scores) return fail(VP_EINVAL, o + "null scores");
+  if (!ids) return fail(VP_EINVAL, o + "null ids");
+  if (!ws) return fail(VP_EINVAL, o + "null ws");
+  if (N < 0) return fail(VP_EINVAL, o + "N must be >= 0");
+  if (masked) {
+    if (int rc = check_mask(o, mask, mask_stride, N)) return rc;
+  }
+  if (int rc = check_topk_k(Q, k, op)) return rc;
+  if (gallery_dtype != VP_F32 && gallery_dtype != VP_BF16)
+    return fail(VP_ENOTSUP, o + "gallery_dtype must be VP_F32 or VP_BF16");
+  if (D < 64 || D % 64) return fail(VP_ENOTSUP, o + "D must be a positive multiple of 64");
+  if (D > vp::kPoolMaxD) return fail(VP_ENOTSUP, o + "D must be <= 1536");
+  if (ld < D) return fail(VP_EINVAL, o + "ld must be >= D");
+  if (ld % 8) return fail(VP_EINVAL, o + "ld must be a multiple of 8 elements");
+  if (misaligned(queries)) return fail(VP_EINVAL, o + "queries must be 16-byte aligned");
+  if (misaligned(gallery)) return fail(VP_EINVAL, o + "gallery must be 16-byte aligned");
+  if (misaligned(ws)) return fail(VP_EINVAL, o + "ws must be 16-byte aligned");
+  const TopkWs L = topk_ws(Q, k);
+  if (ws_bytes < L.total) return fail(VP_EINVAL, o + "ws_bytes too small: need " + std::to_string(L.total));
+  if (Q == 0) return VP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(ws);
+  float* ws_sc = reinterpret_cast<float*>(w + L.scores);
+  int64_t* ws_id = reinterpret_cast<int64_t*>(w + L.ids);
+  int parts = 0;
+  if (masked)
+    VP_HIP(vp::topk_scan_masked(queries, Q, gallery, gallery_dtype == VP_BF16, N, ld, (int)D, (int)k, id_base, mask,
+                                mask_stride, ws_sc, ws_id, &parts, s));
+  else
+    VP_HIP(vp::topk_scan(queries, Q, gallery, gallery_dtype == VP_BF16, N, ld, (int)D, (int)k, id_base, ws_sc, ws_id,
+                         &parts, s));
+  VP_HIP(vp::topk_merge(ws_sc, ws_id, parts, Q, (int)k, (int)k, scores, ids, s));
+  return VP_OK;
+}
+
+// vp_op_topk_groups and vp_op_topk_groups_masked, as topk_call
+int topk_groups_call(const char* op, bool masked, const float* queries, int64_t Q, const void* gallery,
+                     int gallery_dtype, int64_t N, int64_t ld, int64_t D, const int64_t* labels, int64_t k,
+                     int64_t id_base, const uint32_t* mask, int64_t mask_stride, float* scores, int64_t* groups,
+                     int64_t* ids, void* ws, size_t ws_bytes, void* stream) {
+  const std::string o = std::string(op) + ": ";
+  if (!queries) return fail(VP_EINVAL, o + "null queries");
+  if (!gallery && N != 0) return fail(VP_EINVAL, o + "null gallery");
+  if (!labels && N != 0) return fail(VP_EINVAL, o + "null labels");
+  if (!scores) return fail(VP_EINVAL, o + "null scores");
+  if (!groups) return fail(VP_EINVAL, o + "null groups");
+  if (!ids) return fail(VP_EINVAL, o + "null ids");
+  if (!ws) return fail(VP_EINVAL, o + "null ws");
+  if (N < 0) return fail(VP_EINVAL, o + "N must be >= 0");
+  if (masked) {
+    if (int rc = check_mask(o, mask, mask_stride, N)) return rc;
+  }
+  if (int rc = check_topk_k(Q, k, op)) return rc;
+  if (gallery_dtype != VP_F32 && gallery_dtype != VP_BF16)
+    return fail(VP_ENOTSUP, o + "gallery_dtype must be VP_F32 or VP_BF16");
+  if (D < 64 || D % 64) return fail(VP_ENOTSUP, o + "D must be a positive multiple of 64");
+  if (D > vp::kPoolMaxD) return fail(VP_ENOTSUP, o + "D must be <= 1536");
+  if (ld < D) return fail(VP_EINVAL, o + "ld must be >= D");
+  if (ld % 8) return fail(VP_EINVAL, o + "ld must be a multiple of 8 elements");
+  if (misaligned(queries)) return fail(VP_EINVAL, o + "queries must be 16-byte aligned");
+  if (misaligned(gallery)) return fail(VP_EINVAL, o + "gallery must be 16-byte aligned");
+  if (reinterpret_cast<uintptr_t>(labels) & 7) return fail(VP_EINVAL, o + "labels must be 8-byte aligned");
+  if (misaligned(ws)) return fail(VP_EINVAL, o + "ws must be 16-byte aligned");
+  const TopkGroupsWs L = topk_groups_ws(Q, k);
+  if (ws_bytes < L.total) return fail(VP_EINVAL, o + "ws_bytes too small: need " + std::to_string(L.total));
+  if (Q == 0) return VP_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  char* w = static_cast<char*>(ws);
+  float* ws_sc = reinterpret_cast<float*>(w + L.scores);
+  int64_t* ws_id = reinterpret_cast<int64_t*>(w + L.ids);
+  int64_t* ws_gr = reinterpret_cast<int64_t*>(w + L.groups);
+  int parts = 0;
+  if (masked)
+    VP_HIP(vp::topk_groups_scan_masked(queries, Q, gallery, gallery_dtype == VP_BF16, N, ld, (int)D, (int)k, labels,
+                                       id_base, mask, mask_stride, ws_sc, ws_id, ws_gr, &parts, s));
+  else
+    VP_HIP(vp::topk_groups_scan(queries, Q, gallery, gallery_dtype == VP_BF16, N, ld, (int)D, (int)k, labels, id_base,
+                                ws_sc, ws_id, ws_gr, &parts, s));
+  VP_HIP(vp::topk_groups_merge(ws_sc, ws_gr, ws_id, parts, Q, (int)k, (int)k, scores, groups, ids, s));
+  return VP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -57,33 +159,33 @@ int vp_op_topk_workspace_bytes(int64_t Q, int64_t k, size_t* bytes) {
 
 int vp_op_topk(const float* queries, int64_t Q, const void* gallery, int gallery_dtype, int64_t N, int64_t ld, int64_t D,
                int64_t k, int64_t id_base, float* scores, int64_t* ids, void* ws, size_t ws_bytes, void* stream) {
-  if (!queries) return fail(VP_EINVAL, "topk: null queries");
-  if (!gallery && N != 0) return fail(VP_EINVAL, "topk: null gallery");
-  if (!scores) return fail(VP_EINVAL, "topk: null scores");
-  if (!ids) return fail(VP_EINVAL, "topk: null ids");
-  if (!ws) return fail(VP_EINVAL, "topk: null ws");
-  if (N < 0) return fail(VP_EINVAL, "topk: N must be >= 0");
-  if (int rc = check_topk_k(Q, k)) return rc;
-  if (gallery_dtype != VP_F32 && gallery_dtype != VP_BF16)
-    return fail(VP_ENOTSUP, "topk: gallery_dtype must be VP_F32 or VP_BF16");
-  if (D < 64 || D % 64) return fail(VP_ENOTSUP, "topk: D must be a positive multiple of 64");
-  if (D > vp::kPoolMaxD) return fail(VP_ENOTSUP, "topk: D must be <= 1536");
-  if (ld < D) return fail(VP_EINVAL, "topk: ld must be >= D");
-  if (ld % 8) return fail(VP_EINVAL, "topk: ld must be a multiple of 8 elements");
-  if (misaligned(queries)) return fail(VP_EINVAL, "topk: queries must be 16-byte aligned");
-  if (misaligned(gallery)) return fail(VP_EINVAL, "topk: gallery must be 16-byte aligned");
-  if (misaligned(ws)) return fail(VP_EINVAL, "topk: ws must be 16-byte aligned");
-  const TopkWs L = topk_ws(Q, k);
-  if (ws_bytes < L.total) return fail(VP_EINVAL, "topk: ws_bytes too small: need " + std::to_string(L.total));
-  if (Q == 0) return VP_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  float* ws_sc = reinterpret_cast<float*>(w + L.scores);
-  int64_t* ws_id = reinterpret_cast<int64_t*>(w + L.ids);
-  int parts = 0;
-  VP_HIP(vp::topk_scan(queries, Q, gallery, gallery_dtype == VP_BF16, N, ld, (int)D, (int)k, id_base, ws_sc, ws_id,
-                       &parts, s));
-  VP_HIP(vp::topk_merge(ws_sc, ws_id, parts, Q, (int)k, (int)k, scores, ids, s));
+  return topk_call("topk", false, queries, Q, gallery, gallery_dtype, N, ld, D, k, id_base, nullptr, 0, scores, ids, ws,
+                   ws_bytes, stream);
+}
+
+int vp_op_topk_masked(const float* queries, int64_t Q, const void* gallery, int gallery_dtype, int64_t N, int64_t ld,
+                      int64_t D, int64_t k, int64_t id_base, const uint32_t* mask, int64_t mask_query_stride_words,
+                      float* scores, int64_t* ids, void* ws, size_t ws_bytes, void* stream) {
+  return topk_call("topk_masked", true, queries, Q, gallery, gallery_dtype, N, ld, D, k, id_base, mask,
+                   mask_query_stride_words, scores, ids, ws, ws_bytes, stream);
+}
+
+int vp_op_rowmask_pack(const uint8_t* allow, int64_t Q, int64_t N, const uint32_t* and_words, int64_t and_stride,
+                       uint32_t* out_words, int64_t stride, void* stream) {
+  if (Q < 0) return fail(VP_EINVAL, "rowmask_pack: Q must be >= 0");
+  if (N < 0) return fail(VP_EINVAL, "rowmask_pack: N must be >= 0");
+  const int64_t words = (N + 31) / 32;
+  if (stride < words) return fail(VP_EINVAL, "rowmask_pack: stride must be >= ceil(N / 32) words");
+  if (and_stride < 0 || (and_words && and_stride > 0 && and_stride < words))
+    return fail(VP_EINVAL, "rowmask_pack: and_stride must be 0 or >= ceil(N / 32) words");
+  if (Q == 0 || N == 0) return VP_OK;
+  if (!allow) return fail(VP_EINVAL, "rowmask_pack: null allow");
+  if (!out_words) return fail(VP_EINVAL, "rowmask_pack: null out_words");
+  if (reinterpret_cast<uintptr_t>(out_words) & 3) return fail(VP_EINVAL, "rowmask_pack: out_words must be 4-byte aligned");
+  if (reinterpret_cast<uintptr_t>(and_words) & 3) return fail(VP_EINVAL, "rowmask_pack: and_words must be 4-byte aligned");
+  if (N > ((int64_t)1 << 38)) return fail(VP_ENOTSUP, "rowmask_pack: N must be <= 2^38");
+  VP_HIP(vp::rowmask_pack(allow, Q, N, and_words, and_words ? and_stride : 0, out_words, stride,
+                          static_cast<hipStream_t>(stream)));
   return VP_OK;
 }
 
@@ -113,38 +215,16 @@ int vp_op_topk_groups_workspace_bytes(int64_t Q, int64_t k, size_t* bytes) {
 int vp_op_topk_groups(const float* queries, int64_t Q, const void* gallery, int gallery_dtype, int64_t N, int64_t ld,
                       int64_t D, const int64_t* labels, int64_t k, int64_t id_base, float* scores, int64_t* groups,
                       int64_t* ids, void* ws, size_t ws_bytes, void* stream) {
-  if (!queries) return fail(VP_EINVAL, "topk_groups: null queries");
-  if (!gallery && N != 0) return fail(VP_EINVAL, "topk_groups: null gallery");
-  if (!labels && N != 0) return fail(VP_EINVAL, "topk_groups: null labels");
-  if (!scores) return fail(VP_EINVAL, "topk_groups: null scores");
-  if (!groups) return fail(VP_EINVAL, "topk_groups: null groups");
-  if (!ids) return fail(VP_EINVAL, "topk_groups: null ids");
-  if (!ws) return fail(VP_EINVAL, "topk_groups: null ws");
-  if (N < 0) return fail(VP_EINVAL, "topk_groups: N must be >= 0");
-  if (int rc = check_topk_k(Q, k, "topk_groups")) return rc;
-  if (gallery_dtype != VP_F32 && gallery_dtype != VP_BF16)
-    return fail(VP_ENOTSUP, "topk_groups: gallery_dtype must be VP_F32 or VP_BF16");
-  if (D < 64 || D % 64) return fail(VP_ENOTSUP, "topk_groups: D must be a positive multiple of 64");
-  if (D > vp::kPoolMaxD) return fail(VP_ENOTSUP, "topk_groups: D must be <= 1536");
-  if (ld < D) return fail(VP_EINVAL, "topk_groups: ld must be >= D");
-  if (ld % 8) return fail(VP_EINVAL, "topk_groups: ld must be a multiple of 8 elements");
-  if (misaligned(queries)) return fail(VP_EINVAL, "topk_groups: queries must be 16-byte aligned");
-  if (misaligned(gallery)) return fail(VP_EINVAL, "topk_groups: gallery must be 16-byte aligned");
-  if (reinterpret_cast<uintptr_t>(labels) & 7) return fail(VP_EINVAL, "topk_groups: labels must be 8-byte aligned");
-  if (misaligned(ws)) return fail(VP_EINVAL, "topk_groups: ws must be 16-byte aligned");
-  const TopkGroupsWs L = topk_groups_ws(Q, k);
-  if (ws_bytes < L.total) return fail(VP_EINVAL, "topk_groups: ws_bytes too small: need " + std::to_string(L.total));
-  if (Q == 0) return VP_OK;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  char* w = static_cast<char*>(ws);
-  float* ws_sc = reinterpret_cast<float*>(w + L.scores);
-  int64_t* ws_id = reinterpret_cast<int64_t*>(w + L.ids);
-  int64_t* ws_gr = reinterpret_cast<int64_t*>(w + L.groups);
-  int parts = 0;
-  VP_HIP(vp::topk_groups_scan(queries, Q, gallery, gallery_dtype == VP_BF16, N, ld, (int)D, (int)k, labels, id_base,
-                              ws_sc, ws_id, ws_gr, &parts, s));
-  VP_HIP(vp::topk_groups_merge(ws_sc, ws_gr, ws_id, parts, Q, (int)k, (int)k, scores, groups, ids, s));
-  return VP_OK;
+  return topk_groups_call("topk_groups", false, queries, Q, gallery, gallery_dtype, N, ld, D, labels, k, id_base,
+                          nullptr, 0, scores, groups, ids, ws, ws_bytes, stream);
+}
+
+int vp_op_topk_groups_masked(const float* queries, int64_t Q, const void* gallery, int gallery_dtype, int64_t N,
+                             int64_t ld, int64_t D, const int64_t* labels, int64_t k, int64_t id_base,
+                             const uint32_t* mask, int64_t mask_query_stride_words, float* scores, int64_t* groups,
+                             int64_t* ids, void* ws, size_t ws_bytes, void* stream) {
+  return topk_groups_call("topk_groups_masked", true, queries, Q, gallery, gallery_dtype, N, ld, D, labels, k, id_base,
+                          mask, mask_query_stride_words, scores, groups, ids, ws, ws_bytes, stream);
 }
 
 int vp_op_topk_groups_merge(const float* scores_in, const int64_t* groups_in, const int64_t* ids_in, int64_t parts,

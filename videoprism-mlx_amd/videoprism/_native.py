@@ -229,6 +229,13 @@ _SIGNATURES = {
                                   c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vp_op_topk_groups_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    # masked gallery search: a packed bit per row, shared or per query (EmbeddingIndex.remove, search(allow=...))
+    "vp_op_rowmask_pack": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "vp_op_topk_masked": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                  c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_op_topk_groups_masked": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p,
+                                         c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]),
     # not in the public header: queries per workgroup of the search at (D, k) (tools/retrieval_bench.py); no GPU call
     "vp_dev_topk_group": (c_int, [c_int64, c_int64]),
     "vp_dev_topk_groups_group": (c_int, [c_int64, c_int64]),
@@ -784,6 +791,111 @@ def op_topk_groups_merge(scores, groups, ids, k, stream=None):
         call("vp_op_topk_groups_merge", _ptr(scores), _ptr(groups), _ptr(ids), parts, Q, k_in, k, _ptr(out_s),
              _ptr(out_g), _ptr(out_i), _stream(stream))
     return out_s, out_g, out_i
+
+
+def rowmask_words(N) -> int:
+    """Words of one packed row mask of N rows."""
+    return (int(N) + 31) // 32
+
+
+def _check_mask(mask, Q, N):
+    """The query stride in words of a packed mask int32 [words] (shared, stride 0) or [Q, words]."""
+    import torch
+    W = rowmask_words(N)
+    if mask.dtype != torch.int32:
+        raise TypeError(f"mask must be packed int32 words, got {mask.dtype}")
+    if mask.dim() == 1 and mask.shape[0] >= W:
+        if mask.numel() > 1 and mask.stride(0) != 1:
+            raise ValueError("mask words must be contiguous")
+        return 0
+    if mask.dim() == 2 and mask.shape[0] == Q and mask.shape[1] >= W:
+        if mask.shape[1] > 1 and mask.stride(1) != 1:
+            raise ValueError("mask words must be contiguous")
+        return max(mask.stride(0), W) if Q > 1 else max(mask.shape[1], W)
+    raise ValueError(f"mask must be int32 [>= {W}] or [{Q}, >= {W}], got {tuple(mask.shape)}")
+
+
+def op_rowmask_pack(allow, and_words=None, out=None, stream=None):
+    """Packed row masks, int32 [words] of allow [N] or [Q, words] of allow [Q, N] (bool or uint8, nonzero = allowed;
+    words = ceil(N / 32), bit r & 31 of word r >> 5 is row r, bits past N zero), ANDed with and_words (packed int32
+    [words], the same for every row of allow, or [Q, words]) where given."""
+    import torch
+    if allow.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"allow must be bool or uint8, got {allow.dtype}")
+    if allow.dim() not in (1, 2):
+        raise ValueError(f"allow must be [N] or [Q, N], got {tuple(allow.shape)}")
+    shape = tuple(allow.shape)
+    Q, N = (1 if len(shape) == 1 else shape[0]), shape[-1]
+    a = allow.contiguous().view(torch.uint8).reshape(Q, N)
+    W = rowmask_words(N)
+    and_stride = 0
+    if and_words is not None:
+        and_stride = _check_mask(and_words, Q, N)
+        if and_words.device != a.device:
+            raise ValueError("and_words must be on allow's device")
+    if out is None:
+        out = torch.zeros((Q, W), dtype=torch.int32, device=a.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (Q, W) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous int32 [{Q}, {W}]")
+    if Q and N:
+        with torch.cuda.device(a.device):
+            call("vp_op_rowmask_pack", _ptr(a), Q, N, _ptr(and_words), and_stride, _ptr(out), W, _stream(stream))
+    return out.view(W) if len(shape) == 1 else out
+
+
+def op_topk_masked(queries, gallery, k, mask, id_base=0, stream=None, ws=None):
+    """op_topk over the rows that `mask` allows: packed int32 words (op_rowmask_pack), [words] for all queries or
+    [Q, words] for a mask per query.  The result is op_topk's on a gallery of the allowed rows alone, ids mapped
+    back, scores bit for bit.  `ws` as op_topk's (op_topk_workspace_bytes)."""
+    import torch
+    Q, D = queries.shape
+    N = gallery.shape[0]
+    if gallery.dim() != 2 or gallery.shape[1] != D or (N > 1 and gallery.stride(1) != 1):
+        raise ValueError(f"gallery must be [N, {D}] with contiguous rows, got {tuple(gallery.shape)}")
+    if queries.dtype != torch.float32:
+        raise TypeError("queries must be fp32")
+    mstride = _check_mask(mask, Q, N)
+    queries = queries.contiguous()
+    ld = gallery.stride(0) if N > 1 else D
+    scores = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    if Q == 0:
+        return scores, ids
+    if ws is None:
+        ws = torch.empty(op_topk_workspace_bytes(Q, k), dtype=torch.uint8, device=queries.device)
+    with torch.cuda.device(queries.device):
+        call("vp_op_topk_masked", _ptr(queries), Q, _ptr(gallery), _prec(gallery), N, ld, D, k, id_base, _ptr(mask),
+             mstride, _ptr(scores), _ptr(ids), _ptr(ws), ws.numel(), _stream(stream))
+    return scores, ids
+
+
+def op_topk_groups_masked(queries, gallery, labels, k, mask, id_base=0, stream=None, ws=None):
+    """op_topk_groups over the rows that `mask` allows (as op_topk_masked): a row that is not allowed never stands for
+    its group.  `ws` as op_topk_groups's."""
+    import torch
+    Q, D = queries.shape
+    N = gallery.shape[0]
+    if gallery.dim() != 2 or gallery.shape[1] != D or (N > 1 and gallery.stride(1) != 1):
+        raise ValueError(f"gallery must be [N, {D}] with contiguous rows, got {tuple(gallery.shape)}")
+    if queries.dtype != torch.float32:
+        raise TypeError("queries must be fp32")
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (N,):
+        raise ValueError(f"labels must be int64 [{N}], got {labels.dtype} {tuple(labels.shape)}")
+    mstride = _check_mask(mask, Q, N)
+    queries, labels = queries.contiguous(), labels.contiguous()
+    ld = gallery.stride(0) if N > 1 else D
+    scores = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    groups = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    if Q == 0:
+        return scores, groups, ids
+    if ws is None:
+        ws = torch.empty(op_topk_groups_workspace_bytes(Q, k), dtype=torch.uint8, device=queries.device)
+    with torch.cuda.device(queries.device):
+        call("vp_op_topk_groups_masked", _ptr(queries), Q, _ptr(gallery), _prec(gallery), N, ld, D, _ptr(labels), k,
+             id_base, _ptr(mask), mstride, _ptr(scores), _ptr(groups), _ptr(ids), _ptr(ws), ws.numel(),
+             _stream(stream))
+    return scores, groups, ids
 
 
 def op_layernorm(x, gamma1p, beta, out_dtype=None, perm=PERM_NONE, T=1, Nsp=1, add=None,

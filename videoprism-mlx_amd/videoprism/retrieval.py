@@ -6,6 +6,10 @@ appended to one device buffer, and `search` returns each query's k best rows thr
 score-and-select kernels (`vp_op_topk`: the gallery is read once per group of queries and the [N, Q] score matrix is
 never formed).  The search is exact and deterministic: score descending, equal scores by ascending id, and a score
 depends on the two vectors alone, so an index sharded over GPUs returns the bits of an unsharded one.
+
+Rows leave with `remove` (tombstones; `compact` drops them for good) and a search takes `allow`, a subset of the rows
+per call or per query.  Both are one packed bit per row that the scan consults before a row may enter a list
+(`vp_op_topk_masked`), so the result is exactly the search of a gallery that holds the allowed rows alone.
 """
 
 from __future__ import annotations
@@ -45,9 +49,17 @@ class EmbeddingIndex:
         self._buf = torch.empty((max(int(capacity), 0), self.dim), dtype=dtype, device=self.device)
         self._labels = None  # int64 [capacity] once rows are added with `group`
         self._len = 0
+        self._alive = None   # uint8 [capacity] once a row was removed: 0 = removed; rows at and past len are 1
+        self._removed = 0
+        self._live_words = None  # the packed mask of _alive[:len], made when a search needs it
 
     def __len__(self) -> int:
         return self._len
+
+    @property
+    def live(self) -> int:
+        """The rows not removed: len(index) minus the tombstones."""
+        return self._len - self._removed
 
     @property
     def capacity(self) -> int:
@@ -97,6 +109,11 @@ class EmbeddingIndex:
             buf = torch.empty((cap, self.dim), dtype=self.dtype, device=self.device)
             buf[:self._len].copy_(self._buf[:self._len])
             self._buf = buf
+            if self._alive is not None:
+                alive = torch.ones((cap,), dtype=torch.uint8, device=self.device)
+                alive[:self._len].copy_(self._alive[:self._len])
+                self._alive = alive
+        self._live_words = None
         if labels is not None:
             if self._labels is None or self._labels.shape[0] < self.capacity:  # grows with the rows
                 lab = torch.empty((self.capacity,), dtype=torch.int64, device=self.device)
@@ -109,20 +126,93 @@ class EmbeddingIndex:
         self._len = need
         return ids
 
-    def search(self, queries, k: int, comm=None, id_base: int = 0):
+    def remove(self, ids) -> None:
+        """Marks rows as removed: every later search leaves them out, exactly, and a removed row never stands for its
+        group.  `ids` are row numbers (an int, or ints in a sequence, NumPy array or tensor); they stay what they
+        are, `add` keeps appending and `len(index)` does not change (`live` does).  Removing a row twice is
+        harmless; an id outside [0, len) raises ValueError and removes nothing."""
+        import torch
+        if isinstance(ids, torch.Tensor):
+            ids = ids.detach().cpu().numpy()
+        rows = np.atleast_1d(np.asarray(ids))
+        if rows.ndim != 1 or (rows.size and rows.dtype.kind not in "iu"):
+            raise ValueError(f"ids must be integers [n], got {rows.dtype} {tuple(rows.shape)}")
+        rows = rows.astype(np.int64)
+        if rows.size and (rows.min() < 0 or rows.max() >= self._len):
+            bad = rows[(rows < 0) | (rows >= self._len)][0]
+            raise ValueError(f"id {int(bad)} is out of range: the index holds rows 0 .. {self._len - 1}")
+        if not rows.size:
+            return
+        if self._alive is None:
+            self._alive = torch.ones((self.capacity,), dtype=torch.uint8, device=self.device)
+        self._alive[torch.from_numpy(np.unique(rows)).to(self.device)] = 0
+        self._removed = self._len - int(self._alive[:self._len].sum())
+        self._live_words = None
+
+    def compact(self):
+        """Drops the removed rows, and their labels, for good: the survivors move up in order and get new ids
+        0 .. live - 1.  Returns old_ids, int64 [new len]: the id each surviving row had.  Afterwards the index has
+        no tombstones."""
+        import torch
+        if self._alive is None or self._removed == 0:
+            old_ids = torch.arange(self._len, dtype=torch.int64, device=self.device)
+        else:
+            old_ids = self._alive[:self._len].nonzero().reshape(-1)
+            n = int(old_ids.shape[0])
+            self._buf[:n] = self._buf[old_ids]  # the gather is a new tensor, so the rows do not overlap their source
+            if self._labels is not None:
+                self._labels[:n] = self._labels[old_ids]
+            self._len = n
+        self._alive, self._removed, self._live_words = None, 0, None
+        return old_ids
+
+    def _mask(self, allow, Q):
+        """The packed mask of a search, int32 [words] or [Q, words], or None when every row is allowed: the
+        tombstones, `allow`, or the two ANDed by the pack kernel."""
+        import torch
+        live = None
+        if self._removed:
+            if self._live_words is None:
+                self._live_words = _native.op_rowmask_pack(self._alive[:self._len])
+            live = self._live_words
+        if allow is None:
+            return live
+        if isinstance(allow, np.ndarray):
+            if allow.dtype not in (np.bool_, np.uint8):
+                raise TypeError(f"allow must be bool or uint8, got {allow.dtype}")
+            allow = torch.from_numpy(np.ascontiguousarray(allow))
+        if not isinstance(allow, torch.Tensor):
+            raise TypeError(f"allow must be a NumPy array or a tensor, got {type(allow).__name__}")
+        if allow.dtype not in (torch.bool, torch.uint8):
+            raise TypeError(f"allow must be bool or uint8, got {allow.dtype}")
+        if tuple(allow.shape) not in ((self._len,), (Q, self._len)):
+            raise ValueError(f"allow must be [{self._len}] or [{Q}, {self._len}], got {tuple(allow.shape)}")
+        return _native.op_rowmask_pack(allow.to(self.device), and_words=live)
+
+    def search(self, queries, k: int, comm=None, id_base: int = 0, allow=None):
         """(scores [Q, k] fp32, ids [Q, k] int64) of queries [Q, dim]: each query's k largest dot products over the
         gallery, score descending and equal scores by ascending id; ids are id_base + row, and with fewer than k
         rows the tail is (-inf, -1).  NumPy in gives NumPy out, tensors in give tensors out.
 
+        `allow` restricts the search to a subset of the rows: bool or uint8 (nonzero = allowed), NumPy or torch,
+        [len] for all queries or [Q, len] for a subset per query.  Removed rows are left out whatever it says.  The
+        result is the best k of the allowed rows, exactly, with the scores an unrestricted search gives them; rows
+        that are not allowed cost little where 64 in a row are not.
+
         With `comm` (a `distributed.Communicator`) every rank holds a shard: each searches its own rows with its
         `id_base` (the caller's global id of its first row), the [Q, k] lists are gathered over RCCL and every rank
-        merges them, so all ranks return the result of searching the whole gallery, bit for bit."""
+        merges them, so all ranks return the result of searching the whole gallery, bit for bit.  Each rank passes
+        its own shard's slice of `allow`."""
         import torch
         q, from_numpy = _as_tensor(queries, self.device)
         if q.dim() != 2 or q.shape[1] != self.dim:
             raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
         q = q.float().contiguous()
-        scores, ids = _native.op_topk(q, self.embeddings, int(k), id_base=int(id_base))
+        mask = self._mask(allow, int(q.shape[0]))
+        if mask is None:
+            scores, ids = _native.op_topk(q, self.embeddings, int(k), id_base=int(id_base))
+        else:
+            scores, ids = _native.op_topk_masked(q, self.embeddings, int(k), mask, id_base=int(id_base))
         if comm is not None and q.shape[0] > 0:
             Q = int(q.shape[0])
             counts = [Q] * comm.world
@@ -135,14 +225,15 @@ class EmbeddingIndex:
             return scores.cpu().numpy(), ids.cpu().numpy()
         return scores, ids
 
-    def search_groups(self, queries, k: int, comm=None, id_base: int = 0):
+    def search_groups(self, queries, k: int, comm=None, id_base: int = 0, allow=None):
         """(scores [Q, k] fp32, groups [Q, k] int64, ids [Q, k] int64) of queries [Q, dim]: each query's k best groups
         of rows (`add(emb, group=...)`), a group scoring as its best row, with that row's id (id_base + row; of equal
         scores the smallest).  Score descending, equal scores by ascending id; with fewer than k groups the tail is
         (-inf, -1, -1); rows with a negative label, a NaN or a -inf score never count.  Exact for every k up to 128
         however many rows a group holds: the selection happens in the search kernel's lists (`vp_op_topk_groups`).
         For a gallery of sliding windows, `groups` are the videos and `ids` minus a video's first id is the window.
-        NumPy in gives NumPy out, tensors in give tensors out; ValueError on an index without labels.
+        NumPy in gives NumPy out, tensors in give tensors out; ValueError on an index without labels.  `allow` as in
+        `search`: a row that is removed or not allowed never stands for its group.
 
         With `comm` every rank holds a shard (groups may span shards): the three lists are gathered as `search`
         gathers its two and merged on every rank, to the bits of the whole gallery's search."""
@@ -154,7 +245,12 @@ class EmbeddingIndex:
             raise ValueError(f"queries must be [Q, {self.dim}], got {tuple(q.shape)}")
         q = q.float().contiguous()
         k = int(k)
-        scores, groups, ids = _native.op_topk_groups(q, self.embeddings, self.groups, k, id_base=int(id_base))
+        mask = self._mask(allow, int(q.shape[0]))
+        if mask is None:
+            scores, groups, ids = _native.op_topk_groups(q, self.embeddings, self.groups, k, id_base=int(id_base))
+        else:
+            scores, groups, ids = _native.op_topk_groups_masked(q, self.embeddings, self.groups, k, mask,
+                                                                id_base=int(id_base))
         if comm is not None and q.shape[0] > 0:
             Q = int(q.shape[0])
             counts = [Q] * comm.world
