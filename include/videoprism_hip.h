@@ -545,6 +545,50 @@ int vp_op_topk_groups_masked(const float* queries, int64_t Q, const void* galler
                              const uint32_t* mask, int64_t mask_query_stride_words, float* scores, int64_t* groups,
                              int64_t* ids, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------- fp8 gallery: rows quantised once, decoded in the search ----------------
+ * An opt-in storage format of half bf16's width: D + 4 bytes a row (772 B at D = 768 against 1536 B), so a card holds
+ * twice the rows and a search reads half the bytes.  Row r is stored as D codes in OCP e4m3 (torch.float8_e4m3fn: bias
+ * 7, largest finite 448, subnormals down to 2^-9, NaN 0x7f / 0xff, no infinity; gfx950's fp8, not gfx942's fnuz) and one
+ * fp32 scale, and stands for codes[r, :] * scales[r].  The scale MUST be a power of two (2^-100 .. 2^100): every stored
+ * value is then exactly a bf16, the search decodes it exactly and runs the VP_BF16 arithmetic on it (queries as two bf16
+ * terms), so the storage rounding is the only quantisation and a score depends on the two vectors alone, as above.
+ * vp_op_quantize_rows_f8 makes no other scales; what a search returns with another scale is unspecified.
+ * What the rounding costs (unit-norm random rows, the hard case): score error about 4e-3 max / 1e-3 rms at D = 768
+ * (bf16: 3e-4 max), recall@10 against the exact search about 0.95; DESIGN.md §4 "fp8 gallery" has the table.
+ * vp_op_quantize_rows_f8: x device fp32 or bf16 (x_dtype VP_F32 / VP_BF16) [N, D] with row stride ldx elements (ldx >= D,
+ *   rows 16-byte aligned: x 16-byte aligned, ldx a multiple of 4 (fp32) or 8 (bf16)) -> codes [N, D] with row stride
+ *   ldc bytes (ldc >= D, a multiple of 16; 16-byte aligned) and scales [N].  Per row: amax the largest magnitude of
+ *   its finite elements, e the largest integer with amax * 2^e <= 448 clamped to [-100, 100] (0 for a row with no
+ *   finite nonzero element), code = round-to-nearest-even e4m3 of x * 2^e (it never saturates), scale = 2^-e.  A NaN or
+ *   infinite element becomes the NaN code.  Bytes of codes past column D and everything past row N keep what they
+ *   held.  N == 0 launches nothing.
+ * vp_op_topk_f8 / _groups_f8 / _masked_f8 / _groups_masked_f8: the four searches above, argument for argument, with
+ *   `codes, scales` in place of `gallery, gallery_dtype` and ld in bytes (ld >= D, a multiple of 16; codes 16-byte
+ *   aligned, scales 4-byte aligned).  Same limits (D % 64 == 0, D <= 1536, k <= 128, the N bounds), same order, padding,
+ *   merges (vp_op_topk_merge / vp_op_topk_groups_merge) and workspaces (vp_op_topk_workspace_bytes /
+ *   vp_op_topk_groups_workspace_bytes); stateless, no allocation, no synchronisation, every launch on `stream`; Q == 0
+ *   launches nothing, N == 0 gives all padding (codes, scales, labels and mask may then be null).  Neither codes past
+ *   column D or row N nor scales past row N are read.
+ *   A row that holds a NaN code scores NaN and is never returned.  A VP_BF16 gallery can return a row that scores
+ *   +inf; an fp8 gallery cannot hold an infinity, and a row quantised from one has the NaN code there.
+ * The four calls above keep refusing every gallery_dtype but VP_F32 and VP_BF16. */
+int vp_op_quantize_rows_f8(const void* x, int x_dtype, int64_t N, int64_t ldx, int64_t D, uint8_t* codes, int64_t ldc,
+                           float* scales, void* stream);
+int vp_op_topk_f8(const float* queries, int64_t Q, const uint8_t* codes, const float* scales, int64_t N, int64_t ld,
+                  int64_t D, int64_t k, int64_t id_base, float* scores, int64_t* ids, void* ws, size_t ws_bytes,
+                  void* stream);
+int vp_op_topk_groups_f8(const float* queries, int64_t Q, const uint8_t* codes, const float* scales, int64_t N,
+                         int64_t ld, int64_t D, const int64_t* labels, int64_t k, int64_t id_base, float* scores,
+                         int64_t* groups, int64_t* ids, void* ws, size_t ws_bytes, void* stream);
+int vp_op_topk_masked_f8(const float* queries, int64_t Q, const uint8_t* codes, const float* scales, int64_t N,
+                         int64_t ld, int64_t D, int64_t k, int64_t id_base, const uint32_t* mask,
+                         int64_t mask_query_stride_words, float* scores, int64_t* ids, void* ws, size_t ws_bytes,
+                         void* stream);
+int vp_op_topk_groups_masked_f8(const float* queries, int64_t Q, const uint8_t* codes, const float* scales, int64_t N,
+                                int64_t ld, int64_t D, const int64_t* labels, int64_t k, int64_t id_base,
+                                const uint32_t* mask, int64_t mask_query_stride_words, float* scores, int64_t* groups,
+                                int64_t* ids, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------- multi-GPU: RCCL all-gather of pooled clip embeddings ----------------
  * The reference runs on one device; its video-text usage scores every clip against every query,
  * `similarities = video_emb @ text_emb.T` (README.md:81, verify_clip_models.py:84).  With clips

@@ -55,6 +55,15 @@
 // merge does not care how the rows were split.  Bits of rows past N are never looked at (every use of a score
 // is behind `row < p1`) and no word past ceil(N / 32) per mask is read.  rowmask_pack_kernel makes the words from one
 // byte per row, a ballot per 64 rows.
+//
+// The fp8 gallery (vp_op_topk*_f8; DESIGN.md §4 "fp8 gallery") is topk_scan_kernel<kTkF8, GROUPED, MASKED>: the first
+// template argument names the storage, fp32, bf16 or fp8, where it was a bool.  A row is D OCP e4m3 codes and one fp32
+// scale, a power of two, and stands for codes * scale, every value exactly a bf16.  A lane's 16-byte load is 16 codes of
+// its row (a step is 32 elements, the query fragments are laid out for that), v_cvt_scalef32_pk_bf16_fp8 turns them and
+// the row's scale into two bf16x8 operands exactly, and each goes through the bf16 gallery's two MFMAs against the hi
+// and lo fragments: the storage rounding is again the only quantisation, and everything after the scores is the same
+// text.  The scale is read with the row, once per tile, and not for rows that are not read.  quantize_rows_f8_kernel
+// makes codes and scales from fp32 or bf16 rows.
 #include "vp_common.h"
 #include "vp_kernels.h"
 
@@ -119,6 +128,57 @@ __device__ __forceinline__ void tk_mma(const f32x4 (&a)[2][4], const f32x4* bq, 
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
           acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[rt][u][e], b[e], acc[rt], 0, 0, 0);
+    }
+  }
+}
+
+// The fp8 gallery's batch: as tk_load, a step being 32 codes of a row.  A row has D / 32 steps, a multiple of 2 only, so
+// the last batch may hold two steps; its other two are neither loaded nor multiplied (the test is the wave's).
+__device__ __forceinline__ void tk_load_f8(f32x4 (&a)[2][4], const char* const (&rp)[2], const bool (&ok)[2], int t,
+                                           int nt) {
+  const bool four = t + 2 < nt;
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      a[rt][u] = ok[rt] && (u < 2 || four) ? *reinterpret_cast<const f32x4*>(rp[rt] + (int64_t)(t + u) * 32)
+                                           : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+__device__ __forceinline__ const float* tk_scales(const float* scales) { return scales; }
+
+typedef __bf16 tk_bf16x2 __attribute__((ext_vector_type(2)));
+
+// 8 e4m3 codes (two words) times the row's scale, a power of two -> 8 bf16, exactly: a code has four significant bits
+// and the product stays far inside bf16's exponent range (v_cvt_scalef32_pk_bf16_fp8, two codes an instruction)
+__device__ __forceinline__ bf16x8 tk_decode8(float w0, float w1, float scale) {
+  const uint32_t u0 = __float_as_uint(w0), u1 = __float_as_uint(w1);
+  const tk_bf16x2 d[4] = {__builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u0, scale, false),
+                          __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u0, scale, true),
+                          __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u1, scale, false),
+                          __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(u1, scale, true)};
+  return __builtin_bit_cast(bf16x8, d);
+}
+
+// fp8 gallery: the lane's 16 codes of a step are two bf16x8 operands (codes 0 .. 7 and 8 .. 15 of its 16), each against
+// the hi and then the lo fragment of the same 8 query values: v_mfma_f32_32x32x16_bf16 four times a step and row tile
+__device__ __forceinline__ void tk_mma_f8(const f32x4 (&a)[2][4], const float (&scale)[2], const f32x4* bq, int t, int nt,
+                                          int G, int i, int half, bool qlane, f32x16 (&acc)[2]) {
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    if (u == 2 && t + 2 >= nt) break;
+    const int s = t + u;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const f32x4 bh = qlane ? bq[(((s * 2 + j) * 2 + 0) * 2 + half) * G + i] : zero;
+      const f32x4 bl = qlane ? bq[(((s * 2 + j) * 2 + 1) * 2 + half) * G + i] : zero;
+#pragma unroll
+      for (int rt = 0; rt < 2; ++rt) {
+        const bf16x8 av = tk_decode8(a[rt][u][2 * j], a[rt][u][2 * j + 1], scale[rt]);
+        acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8, bh), acc[rt], 0, 0, 0);
+        acc[rt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(bf16x8, bl), acc[rt], 0, 0, 0);
+      }
     }
   }
 }
@@ -253,16 +313,24 @@ __device__ __forceinline__ void tk_mask_load(uint32_t (&m)[2], const uint32_t* m
   for (int rt = 0; rt < 2; ++rt) m[rt] = mlane && r0 + 32 * rt < p1 ? mq[(r0 >> 5) + rt] : 0u;
 }
 
+// how the gallery is stored, the kernel's first template argument: vp_kernels.h's kGalleryF32 / BF16 / F8
+constexpr int kTkF32 = kGalleryF32, kTkBF16 = kGalleryBF16, kTkF8 = kGalleryF8;
+
 // MASKED: a row enters a list only where its bit of `mask` is set (see the file comment); the other instantiations do
-// not look at the two arguments.
-template <bool BF16, bool GROUPED, bool MASKED>
+// not look at the two arguments.  ST == kTkF8: `gallery` holds e4m3 codes, ld in bytes, and row r stands for its codes
+// times scales[r].  That pointer is the one trailing argument `sc` of the fp8 instantiations alone, so the others keep
+// the argument list, and with it the code object, they had before there was an fp8 gallery.
+template <int ST, bool GROUPED, bool MASKED, typename... SC>
 __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __restrict__ queries, int64_t Q,
                                                         const void* __restrict__ gallery, int64_t N, int64_t ld, int D,
                                                         int k, int G, int64_t rows_per_part, int64_t id_base,
                                                         float* __restrict__ ws_sc, int64_t* __restrict__ ws_id,
                                                         const int64_t* __restrict__ labels,
                                                         int64_t* __restrict__ ws_gr,
-                                                        const uint32_t* __restrict__ mask, int64_t mask_stride) {
+                                                        const uint32_t* __restrict__ mask, int64_t mask_stride,
+                                                        SC... sc) {
+  constexpr bool BF16 = ST == kTkBF16, F8 = ST == kTkF8;
+  static_assert(sizeof...(SC) == (F8 ? 1 : 0), "the scales come with the fp8 gallery and with no other");
   extern __shared__ __attribute__((aligned(16))) char tk_smem[];
   f32x4* bq = reinterpret_cast<f32x4*>(tk_smem);                          // D * G * 4 bytes, fragment order
   float* lsc = reinterpret_cast<float*>(tk_smem + (size_t)D * G * 4);     // [G][k]
@@ -279,8 +347,8 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
     lid[e] = kTkNoRow;
     if constexpr (GROUPED) llb[e] = -1;  // matches no row's label: a lane skips a negative one
   }
-  if constexpr (BF16) {
-    const int nc = D >> 3;  // chunks of 8 values: step c >> 1, half c & 1
+  if constexpr (BF16 || F8) {
+    const int nc = D >> 3;  // chunks of 8 values: step c >> 1, half c & 1 (fp8: step c >> 2, half, then operand c & 1)
     for (int e = tid; e < G * nc; e += kTkThreads) {
       const int qi = e / nc, c = e % nc;
       float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -291,9 +359,15 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
       }
       f32x4 hi, lo;
       split8(v, hi, lo);
-      const int s = c >> 1, h = c & 1;
-      bq[((s * 2 + 0) * 2 + h) * G + qi] = hi;
-      bq[((s * 2 + 1) * 2 + h) * G + qi] = lo;
+      if constexpr (F8) {
+        const int s = c >> 2, h = (c >> 1) & 1, j = c & 1;
+        bq[(((s * 2 + j) * 2 + 0) * 2 + h) * G + qi] = hi;
+        bq[(((s * 2 + j) * 2 + 1) * 2 + h) * G + qi] = lo;
+      } else {
+        const int s = c >> 1, h = c & 1;
+        bq[((s * 2 + 0) * 2 + h) * G + qi] = hi;
+        bq[((s * 2 + 1) * 2 + h) * G + qi] = lo;
+      }
     }
   } else {
     const int nc = D >> 2;  // chunks of 4 values
@@ -313,8 +387,8 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
   const int64_t p0 = (int64_t)blockIdx.x * (MASKED ? (int64_t)kTkRows : rows_per_part);
   const int64_t p1 = MASKED ? N : p0 + rows_per_part < N ? p0 + rows_per_part : N;
   const int tstep = MASKED ? (int)rows_per_part : kTkRows;  // at most kTopkMaxParts tiles
-  const int64_t row_bytes = ld * (BF16 ? 2 : 4);
-  const int nt = (D * (BF16 ? 2 : 4)) >> 5;  // 32-byte steps of a row: a multiple of 4
+  const int64_t row_bytes = ld * (F8 ? 1 : BF16 ? 2 : 4);
+  const int nt = (D * (F8 ? 1 : BF16 ? 2 : 4)) >> 5;  // 32-byte steps of a row: a multiple of 4 (fp8: of 2)
   const bool qlane = i < G;
   // MASKED: the lane's mask (its query's, or the shared one in every lane) and the words of the wave's 64 rows of the
   // tile to come, two 32-row words read one tile ahead; a tile starts at a multiple of 512, so r0 is one of 64
@@ -354,14 +428,32 @@ __global__ __launch_bounds__(kTkThreads) void topk_scan_kernel(const float* __re
         rp[rt] = static_cast<const char*>(gallery) + row * row_bytes + 16 * half;
       }
       f32x4 a0[2][4], a1[2][4];
-      tk_load(a0, rp, ok, 0);
-      for (int t = 0; t < nt; t += 8) {
-        const bool more = t + 4 < nt;
-        if (more) tk_load(a1, rp, ok, t + 4);
-        tk_mma<BF16>(a0, bq, t, G, i, half, qlane, acc);
-        if (more) {
-          if (t + 8 < nt) tk_load(a0, rp, ok, t + 8);
-          tk_mma<BF16>(a1, bq, t + 4, G, i, half, qlane, acc);
+      if constexpr (F8) {
+        // the scale of the lane's row comes with the row: not read where the row is not (its codes are zeros then)
+        const float* scales = tk_scales(sc...);
+        float scale[2];
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt) scale[rt] = ok[rt] ? scales[r0 + 32 * rt + i] : 1.f;
+        tk_load_f8(a0, rp, ok, 0, nt);
+        for (int t = 0; t < nt; t += 8) {
+          const bool more = t + 4 < nt;
+          if (more) tk_load_f8(a1, rp, ok, t + 4, nt);
+          tk_mma_f8(a0, scale, bq, t, nt, G, i, half, qlane, acc);
+          if (more) {
+            if (t + 8 < nt) tk_load_f8(a0, rp, ok, t + 8, nt);
+            tk_mma_f8(a1, scale, bq, t + 4, nt, G, i, half, qlane, acc);
+          }
+        }
+      } else {
+        tk_load(a0, rp, ok, 0);
+        for (int t = 0; t < nt; t += 8) {
+          const bool more = t + 4 < nt;
+          if (more) tk_load(a1, rp, ok, t + 4);
+          tk_mma<BF16>(a0, bq, t, G, i, half, qlane, acc);
+          if (more) {
+            if (t + 8 < nt) tk_load(a0, rp, ok, t + 8);
+            tk_mma<BF16>(a1, bq, t + 4, G, i, half, qlane, acc);
+          }
         }
       }
     }
@@ -620,6 +712,104 @@ __global__ __launch_bounds__(kPackRows) void rowmask_pack_kernel(const uint8_t* 
   }
 }
 
+// Rows to the fp8 gallery's storage (vp_op_quantize_rows_f8; DESIGN.md §4 "fp8 gallery"): row r becomes D e4m3 codes
+// and one scale 2^-e, e the largest integer with amax * 2^e <= 448 (amax over the row's finite elements), clamped to
+// +-100 and 0 for a row without a finite nonzero element; code = RNE_e4m3(x * 2^e), the NaN code for a non-finite x.
+// A wave takes a row and reads it once: a lane keeps up to two chunks of 16 values in registers, the wave reduces the
+// largest magnitude as an integer (the bits of |x| order as the values do), e comes from its exponent and mantissa
+// fields (amax = m * 2^p, m in [0.5, 1): 9 - p where m <= 0.875, else 8 - p), the products are exact and
+// v_cvt_pk_fp8_f32 rounds them; no product passes 448 (but where e was clamped, which plain C++ handles), so the
+// instruction never saturates, and it never sees a non-finite value either.  A lane stores its chunk's 16 codes as one
+// 16-byte word and lane 0 the scale; columns past D and rows past N are not written.
+constexpr int kQzRows = 4;  // rows of a workgroup: a wave each
+
+template <bool XBF16>
+__global__ __launch_bounds__(64 * kQzRows) void quantize_rows_f8_kernel(const void* __restrict__ x, int64_t N,
+                                                                        int64_t ldx, int D, uint8_t* __restrict__ codes,
+                                                                        int64_t ldc, float* __restrict__ scales) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * kQzRows + (threadIdx.x >> 6);
+  if (row >= N) return;  // the whole wave
+  const int nch = D >> 4;  // chunks of 16 values: at most 96
+  float v[2][16];
+  uint32_t amax = 0;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int ch = lane + 64 * c;
+    if (ch < nch) {
+      if constexpr (XBF16) {
+        const f32x4* src = reinterpret_cast<const f32x4*>(static_cast<const bf16_t*>(x) + row * ldx + 16 * ch);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const f32x4 p = src[h];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const uint32_t u = __float_as_uint(p[e]);
+            v[c][8 * h + 2 * e] = __uint_as_float(u << 16);
+            v[c][8 * h + 2 * e + 1] = __uint_as_float(u & 0xffff0000u);
+          }
+        }
+      } else {
+        const f32x4* src = reinterpret_cast<const f32x4*>(static_cast<const float*>(x) + row * ldx + 16 * ch);
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+          const f32x4 p = src[h];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[c][4 * h + e] = p[e];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) v[c][e] = 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const uint32_t u = __float_as_uint(v[c][e]) & 0x7fffffffu;
+      if (u < 0x7f800000u && u > amax) amax = u;
+    }
+  }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)amax, m);
+    amax = o > amax ? o : amax;
+  }
+  int e = 0;
+  if (amax != 0) {
+    const int E = (int)(amax >> 23);  // 0: a denormal, p <= -126, and e clamps
+    e = E == 0 ? 100 : ((amax & 0x7fffffu) <= 0x600000u ? 135 : 134) - E;
+    e = e < -100 ? -100 : e > 100 ? 100 : e;
+  }
+  const float mul = __uint_as_float((uint32_t)(127 + e) << 23);
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int ch = lane + 64 * c;
+    if (ch >= nch) continue;
+    uint32_t w[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      float y[4];
+      uint32_t nanb = 0;  // the NaN code in the bytes of non-finite elements, whatever the instruction makes of them
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const float xv = v[c][4 * g + b];
+        float p = xv * mul;
+        // only where e was clamped at -100 (amax above 448 * 2^100) can a product pass 448: from 464, the tie with
+        // the absent next value, the format's round-to-nearest gives the NaN code, below it 448
+        const bool fin = (__float_as_uint(xv) & 0x7fffffffu) < 0x7f800000u && fabsf(p) < 464.f;
+        p = fabsf(p) > 448.f ? copysignf(448.f, p) : p;
+        y[b] = fin ? p : 0.f;
+        nanb |= fin ? 0u : 0xffu << (8 * b);
+      }
+      int pk = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+      pk = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], pk, true);
+      w[g] = ((uint32_t)pk & ~nanb) | (0x7f7f7f7fu & nanb);
+    }
+    *reinterpret_cast<f32x4*>(codes + row * ldc + 16 * ch) =
+        f32x4{__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3])};
+  }
+  if (lane == 0) scales[row] = __uint_as_float((uint32_t)(127 - e) << 23);
+}
+
 }  // namespace
 
 int topk_group(int D, int k) {
@@ -635,9 +825,11 @@ namespace {
 
 // both searches: labels == nullptr is the ungrouped one (ws_gr unused); MASKED: mask / mask_stride as the kernel's
 template <bool GROUPED, bool MASKED>
-hipError_t topk_scan_launch(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
-                            int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id, int64_t* ws_gr,
-                            const uint32_t* mask, int64_t mask_stride, int* parts_out, hipStream_t s) {
+hipError_t topk_scan_launch(const float* queries, int64_t Q, const void* gallery, int st, const float* scales, int64_t N,
+                            int64_t ld, int D, int k, const int64_t* labels, int64_t id_base, float* ws_sc,
+                            int64_t* ws_id, int64_t* ws_gr, const uint32_t* mask, int64_t mask_stride, int* parts_out,
+                            hipStream_t s) {
+  if (st < kGalleryF32 || st > kGalleryF8 || (st == kGalleryF8 && !scales && N > 0)) return hipErrorInvalidValue;
   if (Q < 1 || N < 0 || D < 64 || D % 64 || D > kPoolMaxD || k < 1 || k > kTopkMaxK || ld < D) return hipErrorInvalidValue;
   if (MASKED && ((!mask && N > 0) || mask_stride < 0 || (mask_stride > 0 && mask_stride < (N + 31) / 32)))
     return hipErrorInvalidValue;
@@ -660,16 +852,21 @@ hipError_t topk_scan_launch(const float* queries, int64_t Q, const void* gallery
     parts = tiles < 1 ? 1 : (N + rows_per_part - 1) / rows_per_part;
   }
   const int lds = D * G * 4 + G * k * (GROUPED ? 16 : 8) + 2 * kTkWaves * 4;
-  const void* fn = bf16 ? reinterpret_cast<const void*>(&topk_scan_kernel<true, GROUPED, MASKED>)
-                        : reinterpret_cast<const void*>(&topk_scan_kernel<false, GROUPED, MASKED>);
+  const void* fn = st == kTkF8     ? reinterpret_cast<const void*>(&topk_scan_kernel<kTkF8, GROUPED, MASKED, const float*>)
+                   : st == kTkBF16 ? reinterpret_cast<const void*>(&topk_scan_kernel<kTkBF16, GROUPED, MASKED>)
+                                   : reinterpret_cast<const void*>(&topk_scan_kernel<kTkF32, GROUPED, MASKED>);
   hipError_t e = ensure_dyn_lds(fn, kTkLdsBytes);
   if (e != hipSuccess) return e;
   const dim3 grid((unsigned)parts, (unsigned)groups);
-  if (bf16)
-    hipLaunchKernelGGL((topk_scan_kernel<true, GROUPED, MASKED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery, N,
-                       ld, D, k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr, mask, mask_stride);
+  if (st == kTkF8)
+    hipLaunchKernelGGL((topk_scan_kernel<kTkF8, GROUPED, MASKED, const float*>), grid, dim3(kTkThreads), lds, s, queries,
+                       Q, gallery, N, ld, D, k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr, mask, mask_stride,
+                       scales);
+  else if (st == kTkBF16)
+    hipLaunchKernelGGL((topk_scan_kernel<kTkBF16, GROUPED, MASKED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery,
+                       N, ld, D, k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr, mask, mask_stride);
   else
-    hipLaunchKernelGGL((topk_scan_kernel<false, GROUPED, MASKED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery,
+    hipLaunchKernelGGL((topk_scan_kernel<kTkF32, GROUPED, MASKED>), grid, dim3(kTkThreads), lds, s, queries, Q, gallery,
                        N, ld, D, k, G, rows_per_part, id_base, ws_sc, ws_id, labels, ws_gr, mask, mask_stride);
   *parts_out = (int)parts;
   return hipGetLastError();
@@ -677,34 +874,52 @@ hipError_t topk_scan_launch(const float* queries, int64_t Q, const void* gallery
 
 }  // namespace
 
-hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D, int k,
-                     int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s) {
-  return topk_scan_launch<false, false>(queries, Q, gallery, bf16, N, ld, D, k, nullptr, id_base, ws_sc, ws_id, nullptr,
-                                        nullptr, 0, parts_out, s);
+hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int storage, int64_t N, int64_t ld, int D,
+                     int k, int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s,
+                     const float* scales) {
+  return topk_scan_launch<false, false>(queries, Q, gallery, storage, scales, N, ld, D, k, nullptr, id_base, ws_sc, ws_id,
+                                        nullptr, nullptr, 0, parts_out, s);
 }
 
-hipError_t topk_groups_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
-                            int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id, int64_t* ws_gr,
-                            int* parts_out, hipStream_t s) {
+hipError_t topk_groups_scan(const float* queries, int64_t Q, const void* gallery, int storage, int64_t N, int64_t ld,
+                            int D, int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id,
+                            int64_t* ws_gr, int* parts_out, hipStream_t s, const float* scales) {
   if (!labels && N > 0) return hipErrorInvalidValue;
-  return topk_scan_launch<true, false>(queries, Q, gallery, bf16, N, ld, D, k, labels, id_base, ws_sc, ws_id, ws_gr,
-                                       nullptr, 0, parts_out, s);
+  return topk_scan_launch<true, false>(queries, Q, gallery, storage, scales, N, ld, D, k, labels, id_base, ws_sc, ws_id,
+                                       ws_gr, nullptr, 0, parts_out, s);
 }
 
-hipError_t topk_scan_masked(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
-                            int k, int64_t id_base, const uint32_t* mask, int64_t mask_stride, float* ws_sc,
-                            int64_t* ws_id, int* parts_out, hipStream_t s) {
-  return topk_scan_launch<false, true>(queries, Q, gallery, bf16, N, ld, D, k, nullptr, id_base, ws_sc, ws_id, nullptr,
-                                       mask, mask_stride, parts_out, s);
+hipError_t topk_scan_masked(const float* queries, int64_t Q, const void* gallery, int storage, int64_t N, int64_t ld,
+                            int D, int k, int64_t id_base, const uint32_t* mask, int64_t mask_stride, float* ws_sc,
+                            int64_t* ws_id, int* parts_out, hipStream_t s, const float* scales) {
+  return topk_scan_launch<false, true>(queries, Q, gallery, storage, scales, N, ld, D, k, nullptr, id_base, ws_sc, ws_id,
+                                       nullptr, mask, mask_stride, parts_out, s);
 }
 
-hipError_t topk_groups_scan_masked(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld,
-                                   int D, int k, const int64_t* labels, int64_t id_base, const uint32_t* mask,
-                                   int64_t mask_stride, float* ws_sc, int64_t* ws_id, int64_t* ws_gr, int* parts_out,
-                                   hipStream_t s) {
+hipError_t topk_groups_scan_masked(const float* queries, int64_t Q, const void* gallery, int storage, int64_t N,
+                                   int64_t ld, int D, int k, const int64_t* labels, int64_t id_base,
+                                   const uint32_t* mask, int64_t mask_stride, float* ws_sc, int64_t* ws_id,
+                                   int64_t* ws_gr, int* parts_out, hipStream_t s, const float* scales) {
   if (!labels && N > 0) return hipErrorInvalidValue;
-  return topk_scan_launch<true, true>(queries, Q, gallery, bf16, N, ld, D, k, labels, id_base, ws_sc, ws_id, ws_gr, mask,
-                                      mask_stride, parts_out, s);
+  return topk_scan_launch<true, true>(queries, Q, gallery, storage, scales, N, ld, D, k, labels, id_base, ws_sc, ws_id,
+                                      ws_gr, mask, mask_stride, parts_out, s);
+}
+
+hipError_t quantize_rows_f8(const void* x, int x_bf16, int64_t N, int64_t ldx, int D, uint8_t* codes, int64_t ldc,
+                            float* scales, hipStream_t s) {
+  if (N < 0 || D < 64 || D % 64 || D > kPoolMaxD || ldx < D || ldc < D || ldc % 16 || ldx % (x_bf16 ? 8 : 4))
+    return hipErrorInvalidValue;
+  if (N == 0) return hipSuccess;
+  if (!x || !codes || !scales) return hipErrorInvalidValue;
+  const int64_t bx = (N + kQzRows - 1) / kQzRows;
+  if (bx > 0x7fffffff) return hipErrorInvalidValue;
+  if (x_bf16)
+    hipLaunchKernelGGL(quantize_rows_f8_kernel<true>, dim3((unsigned)bx), dim3(64 * kQzRows), 0, s, x, N, ldx, D, codes,
+                       ldc, scales);
+  else
+    hipLaunchKernelGGL(quantize_rows_f8_kernel<false>, dim3((unsigned)bx), dim3(64 * kQzRows), 0, s, x, N, ldx, D, codes,
+                       ldc, scales);
+  return hipGetLastError();
 }
 
 hipError_t rowmask_pack(const uint8_t* allow, int64_t Q, int64_t N, const uint32_t* and_words, int64_t and_stride,

@@ -283,9 +283,14 @@ constexpr int kTopkMaxParts = 256;  // most row ranges a search splits the galle
 int topk_group(int D, int k);
 // pass 1: per row range p < *parts_out (<= kTopkMaxParts) the best k of rows [p * n, (p + 1) * n) per query, sorted by
 // (score descending, row ascending) and padded with (-inf, -1): ws_sc / ws_id [parts][Q][k], ids = id_base + row.
-// queries fp32 [Q][D]; gallery fp32 or bf16 [N][ld]; D = 64 j <= kPoolMaxD; N = 0 gives one list of padding
-hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D, int k,
-                     int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s);
+// queries fp32 [Q][D]; gallery fp32 or bf16 [N][ld]; D = 64 j <= kPoolMaxD; N = 0 gives one list of padding.
+// `storage` says how the gallery is stored: kGalleryF32 (0) and kGalleryBF16 (1) as above, or kGalleryF8: e4m3 codes
+// [N][ld] (ld in bytes, a multiple of 16) and `scales` fp32 [N], powers of two, row r standing for codes[r] * scales[r]
+// (DESIGN.md §4 "fp8 gallery"); the other two do not look at `scales`
+constexpr int kGalleryF32 = 0, kGalleryBF16 = 1, kGalleryF8 = 2;
+hipError_t topk_scan(const float* queries, int64_t Q, const void* gallery, int storage, int64_t N, int64_t ld, int D,
+                     int k, int64_t id_base, float* ws_sc, int64_t* ws_id, int* parts_out, hipStream_t s,
+                     const float* scales = nullptr);
 // pass 2: the best k <= k_in of `parts` such lists [parts][Q][k_in] per query, same order, ties between lists by id
 hipError_t topk_merge(const float* sin, const int64_t* iin, int64_t parts, int64_t Q, int k_in, int k, float* so,
                       int64_t* io, hipStream_t s);
@@ -294,9 +299,9 @@ hipError_t topk_merge(const float* sin, const int64_t* iin, int64_t parts, int64
 // row, group).  Same passes and the same scores as above; the lists carry an int64 label per entry in LDS, so the
 // queries of a workgroup are chosen against 16 B an entry
 int topk_groups_group(int D, int k);
-hipError_t topk_groups_scan(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
-                            int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id, int64_t* ws_gr,
-                            int* parts_out, hipStream_t s);
+hipError_t topk_groups_scan(const float* queries, int64_t Q, const void* gallery, int storage, int64_t N, int64_t ld,
+                            int D, int k, const int64_t* labels, int64_t id_base, float* ws_sc, int64_t* ws_id,
+                            int64_t* ws_gr, int* parts_out, hipStream_t s, const float* scales = nullptr);
 // the merge drops an entry when another list holds its group with an entry that comes before it, so the result is a
 // function of the set of (score, group, id) alone
 hipError_t topk_groups_merge(const float* sin, const int64_t* gin, const int64_t* iin, int64_t parts, int64_t Q, int k_in,
@@ -305,13 +310,17 @@ hipError_t topk_groups_merge(const float* sin, const int64_t* gin, const int64_t
 // r & 31 of word r >> 5; ceil(N / 32) words a mask, bits past N ignored).  mask_stride 0: one mask for all queries;
 // else query q's mask starts at word q * mask_stride (>= ceil(N / 32)).  Lists, scores of allowed rows and the merges
 // are the unmasked ones'; N = 0 takes a null mask
-hipError_t topk_scan_masked(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld, int D,
-                            int k, int64_t id_base, const uint32_t* mask, int64_t mask_stride, float* ws_sc,
-                            int64_t* ws_id, int* parts_out, hipStream_t s);
-hipError_t topk_groups_scan_masked(const float* queries, int64_t Q, const void* gallery, int bf16, int64_t N, int64_t ld,
-                                   int D, int k, const int64_t* labels, int64_t id_base, const uint32_t* mask,
-                                   int64_t mask_stride, float* ws_sc, int64_t* ws_id, int64_t* ws_gr, int* parts_out,
-                                   hipStream_t s);
+hipError_t topk_scan_masked(const float* queries, int64_t Q, const void* gallery, int storage, int64_t N, int64_t ld,
+                            int D, int k, int64_t id_base, const uint32_t* mask, int64_t mask_stride, float* ws_sc,
+                            int64_t* ws_id, int* parts_out, hipStream_t s, const float* scales = nullptr);
+hipError_t topk_groups_scan_masked(const float* queries, int64_t Q, const void* gallery, int storage, int64_t N,
+                                   int64_t ld, int D, int k, const int64_t* labels, int64_t id_base,
+                                   const uint32_t* mask, int64_t mask_stride, float* ws_sc, int64_t* ws_id,
+                                   int64_t* ws_gr, int* parts_out, hipStream_t s, const float* scales = nullptr);
+// the fp8 gallery's rows from x fp32 or bf16 [N][ldx] (16-byte aligned rows): codes [N][ldc] e4m3 (ldc a multiple of
+// 16 bytes; columns past D keep what they held) and scales [N], one power of two per row (retrieval_kernels.hip)
+hipError_t quantize_rows_f8(const void* x, int x_bf16, int64_t N, int64_t ldx, int D, uint8_t* codes, int64_t ldc,
+                            float* scales, hipStream_t s);
 // out[q * stride + w] = the packed bits of allow[q][32 w ..] != 0 (uint8 [Q][N], rows past N zero), ANDed with
 // and_words[q * and_stride + w] where and_words is given (and_stride 0: the same words for every q)
 hipError_t rowmask_pack(const uint8_t* allow, int64_t Q, int64_t N, const uint32_t* and_words, int64_t and_stride,

@@ -236,6 +236,18 @@ _SIGNATURES = {
     "vp_op_topk_groups_masked": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p,
                                          c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_size_t, c_void_p]),
+    # fp8 gallery: e4m3 codes and a power-of-two scale per row (EmbeddingIndex(dtype=torch.float8_e4m3fn))
+    "vp_op_quantize_rows_f8": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p,
+                                       c_void_p]),
+    "vp_op_topk_f8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
+                              c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_op_topk_groups_f8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                     c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_op_topk_masked_f8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                     c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vp_op_topk_groups_masked_f8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                            c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_size_t, c_void_p]),
     # not in the public header: queries per workgroup of the search at (D, k) (tools/retrieval_bench.py); no GPU call
     "vp_dev_topk_group": (c_int, [c_int64, c_int64]),
     "vp_dev_topk_groups_group": (c_int, [c_int64, c_int64]),
@@ -896,6 +908,141 @@ def op_topk_groups_masked(queries, gallery, labels, k, mask, id_base=0, stream=N
              id_base, _ptr(mask), mstride, _ptr(scores), _ptr(groups), _ptr(ids), _ptr(ws), ws.numel(),
              _stream(stream))
     return scores, groups, ids
+
+
+def _codes_u8(codes):
+    """An e4m3 code buffer as the bytes the library takes (torch.float8_e4m3fn or uint8, the same storage)."""
+    import torch
+    if codes.dtype == torch.float8_e4m3fn:
+        return codes.view(torch.uint8)
+    if codes.dtype != torch.uint8:
+        raise TypeError(f"codes must be float8_e4m3fn or uint8, got {codes.dtype}")
+    return codes
+
+
+def op_quantize_rows_f8(x, codes=None, scales=None, stream=None):
+    """x [N, D] (fp32 or bf16, unit stride along D, rows 16-byte aligned) as the fp8 gallery stores it: (codes [N, D]
+    float8_e4m3fn, scales [N] fp32), row r standing for codes[r] * scales[r] with scales[r] the power of two that puts
+    the row's largest finite magnitude in (224, 448].  `codes` / `scales`: where to write (codes with any row stride
+    that is a multiple of 16 bytes; its columns past D keep what they hold); allocated when None."""
+    import torch
+    if x.dim() != 2 or (x.shape[0] > 1 and x.stride(1) != 1):
+        raise ValueError(f"x must be [N, D] with contiguous rows, got {tuple(x.shape)}")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"x must be fp32 or bf16, got {x.dtype}")
+    N, D = x.shape
+    if codes is None:
+        codes = torch.empty((N, D), dtype=torch.float8_e4m3fn, device=x.device)
+    if scales is None:
+        scales = torch.empty((N,), dtype=torch.float32, device=x.device)
+    cb = _codes_u8(codes)
+    if tuple(cb.shape) != (N, D) or (N > 1 and cb.stride(1) != 1):
+        raise ValueError(f"codes must be [{N}, {D}] with contiguous rows, got {tuple(cb.shape)}")
+    if scales.dtype != torch.float32 or tuple(scales.shape) != (N,) or not scales.is_contiguous():
+        raise ValueError(f"scales must be contiguous fp32 [{N}], got {scales.dtype} {tuple(scales.shape)}")
+    if N:
+        ldx = x.stride(0) if N > 1 else D
+        ldc = cb.stride(0) if N > 1 else D
+        with torch.cuda.device(x.device):
+            call("vp_op_quantize_rows_f8", _ptr(x), _prec(x), N, ldx, D, _ptr(cb), ldc, _ptr(scales), _stream(stream))
+    return codes, scales
+
+
+def _f8_gallery(queries, codes, scales):
+    """(codes as bytes, N, ld in bytes) of an fp8 gallery after the shape checks the four searches share."""
+    import torch
+    Q, D = queries.shape
+    cb = _codes_u8(codes)
+    N = cb.shape[0]
+    if cb.dim() != 2 or cb.shape[1] != D or (N > 1 and cb.stride(1) != 1):
+        raise ValueError(f"codes must be [N, {D}] with contiguous rows, got {tuple(cb.shape)}")
+    if scales.dtype != torch.float32 or tuple(scales.shape) != (N,) or (N > 1 and scales.stride(0) != 1):
+        raise ValueError(f"scales must be contiguous fp32 [{N}], got {scales.dtype} {tuple(scales.shape)}")
+    if queries.dtype != torch.float32:
+        raise TypeError("queries must be fp32")
+    return cb, N, (cb.stride(0) if N > 1 else D)
+
+
+def op_topk_f8(queries, codes, scales, k, id_base=0, stream=None, ws=None):
+    """op_topk over an fp8 gallery: codes [N, D] (float8_e4m3fn or its bytes, any row stride that is a multiple of 16)
+    and scales [N] fp32, powers of two, as op_quantize_rows_f8 makes them.  Order, padding and `ws` as op_topk."""
+    import torch
+    Q, D = queries.shape
+    cb, N, ld = _f8_gallery(queries, codes, scales)
+    queries = queries.contiguous()
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    if Q == 0:
+        return out_s, ids
+    if ws is None:
+        ws = torch.empty(op_topk_workspace_bytes(Q, k), dtype=torch.uint8, device=queries.device)
+    with torch.cuda.device(queries.device):
+        call("vp_op_topk_f8", _ptr(queries), Q, _ptr(cb), _ptr(scales), N, ld, D, k, id_base, _ptr(out_s), _ptr(ids),
+             _ptr(ws), ws.numel(), _stream(stream))
+    return out_s, ids
+
+
+def op_topk_groups_f8(queries, codes, scales, labels, k, id_base=0, stream=None, ws=None):
+    """op_topk_groups over an fp8 gallery (codes and scales as op_topk_f8)."""
+    import torch
+    Q, D = queries.shape
+    cb, N, ld = _f8_gallery(queries, codes, scales)
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (N,):
+        raise ValueError(f"labels must be int64 [{N}], got {labels.dtype} {tuple(labels.shape)}")
+    queries, labels = queries.contiguous(), labels.contiguous()
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    groups = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    if Q == 0:
+        return out_s, groups, ids
+    if ws is None:
+        ws = torch.empty(op_topk_groups_workspace_bytes(Q, k), dtype=torch.uint8, device=queries.device)
+    with torch.cuda.device(queries.device):
+        call("vp_op_topk_groups_f8", _ptr(queries), Q, _ptr(cb), _ptr(scales), N, ld, D, _ptr(labels), k, id_base,
+             _ptr(out_s), _ptr(groups), _ptr(ids), _ptr(ws), ws.numel(), _stream(stream))
+    return out_s, groups, ids
+
+
+def op_topk_masked_f8(queries, codes, scales, k, mask, id_base=0, stream=None, ws=None):
+    """op_topk_masked over an fp8 gallery (codes and scales as op_topk_f8)."""
+    import torch
+    Q, D = queries.shape
+    cb, N, ld = _f8_gallery(queries, codes, scales)
+    mstride = _check_mask(mask, Q, N)
+    queries = queries.contiguous()
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    if Q == 0:
+        return out_s, ids
+    if ws is None:
+        ws = torch.empty(op_topk_workspace_bytes(Q, k), dtype=torch.uint8, device=queries.device)
+    with torch.cuda.device(queries.device):
+        call("vp_op_topk_masked_f8", _ptr(queries), Q, _ptr(cb), _ptr(scales), N, ld, D, k, id_base, _ptr(mask),
+             mstride, _ptr(out_s), _ptr(ids), _ptr(ws), ws.numel(), _stream(stream))
+    return out_s, ids
+
+
+def op_topk_groups_masked_f8(queries, codes, scales, labels, k, mask, id_base=0, stream=None, ws=None):
+    """op_topk_groups_masked over an fp8 gallery (codes and scales as op_topk_f8)."""
+    import torch
+    Q, D = queries.shape
+    cb, N, ld = _f8_gallery(queries, codes, scales)
+    if labels.dtype != torch.int64 or tuple(labels.shape) != (N,):
+        raise ValueError(f"labels must be int64 [{N}], got {labels.dtype} {tuple(labels.shape)}")
+    mstride = _check_mask(mask, Q, N)
+    queries, labels = queries.contiguous(), labels.contiguous()
+    out_s = torch.empty((Q, k), dtype=torch.float32, device=queries.device)
+    groups = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    ids = torch.empty((Q, k), dtype=torch.int64, device=queries.device)
+    if Q == 0:
+        return out_s, groups, ids
+    if ws is None:
+        ws = torch.empty(op_topk_groups_workspace_bytes(Q, k), dtype=torch.uint8, device=queries.device)
+    with torch.cuda.device(queries.device):
+        call("vp_op_topk_groups_masked_f8", _ptr(queries), Q, _ptr(cb), _ptr(scales), N, ld, D, _ptr(labels), k,
+             id_base, _ptr(mask), mstride, _ptr(out_s), _ptr(groups), _ptr(ids), _ptr(ws), ws.numel(),
+             _stream(stream))
+    return out_s, groups, ids
 
 
 def op_layernorm(x, gamma1p, beta, out_dtype=None, perm=PERM_NONE, T=1, Nsp=1, add=None,
