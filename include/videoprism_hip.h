@@ -265,6 +265,28 @@ typedef struct {
 int vp_op_preprocess_yuv(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t W, const int32_t* frame_idx,
                          int64_t F, int mode, int64_t S, uint8_t* dst, void* stream);
 
+/* Both calls with the geometry per output frame (multi-view evaluation, crop and flip augmentation).
+ *   views      device int32 [V, 9]: rows box_y, box_x, box_h, box_w, new_h, new_w, win_y, win_x, flags
+ *   frame_idx  device int32 [V*T] (clamped to [0, N-1]), or NULL = frame t of every view is source frame t (then T <= N)
+ *   dst        device uint8 [V*T, S, S, 3], contiguous; frame v*T + t belongs to view v
+ * With img the source frame (for YUV the full-resolution RGB frame that is never stored), a view's picture is
+ *   out = cv2.resize(img[box_y:box_y+box_h, box_x:box_x+box_w], (new_w, new_h))[win_y:win_y+S, win_x:win_x+S]
+ *   out = out[:, ::-1] if flags & 1        (horizontal mirror; the other bits of flags must be 0)
+ * in the arithmetic of vp_op_preprocess_frames: the taps clamp at the box's edges, not the frame's, and an
+ * axis scale is the double 1.0 / ((double)new_w / (double)box_w), so the whole frame with the centre-crop
+ * geometry gives vp_op_preprocess_frames' bits.  For YUV a tap at box-relative (y, x) is the luma sample
+ * (box_y + y, box_x + x) with the chroma sample ((box_y + y) >> 1, (box_x + x) >> 1).
+ * The table is never read on the host.  The kernel clamps each row, so that no table causes a read outside the
+ * frames, and a valid row passes unchanged: box_y to [0, H-1], box_h to [1, H-box_y] (x likewise), new_h and
+ * new_w to [S, 2^24-1], win_y to [0, new_h-S] and win_x to [0, new_w-S].
+ * The size limits are vp_op_preprocess_frames' with F = V*T.  Asynchronous on `stream` on the current device;
+ * never allocates, never synchronises; argument errors are VP_EINVAL before any device call. */
+int vp_op_preprocess_views(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
+                           int64_t frame_stride, const int32_t* frame_idx, const int32_t* views, int64_t V,
+                           int64_t T, int swap_rb, int64_t S, uint8_t* dst, void* stream);
+int vp_op_preprocess_yuv_views(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t W, const int32_t* frame_idx,
+                               const int32_t* views, int64_t V, int64_t T, int64_t S, uint8_t* dst, void* stream);
+
 /* The integer table vp_op_preprocess_yuv uses: out[0..8] = rows R, G, B x (cy, cu, cv), each
  * floor(x * 65536 + 0.5) of the real coefficient, out[9] = yoff, out[10] = coff; bit_depth 8 or 10.
  * No device needed. */

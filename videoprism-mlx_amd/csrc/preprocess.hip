@@ -15,6 +15,13 @@
 // of yuv_coefficients (tests/yuv_restatement.py states the arithmetic), and the blend runs on those.  A
 // tap is one luma sample and one chroma pair; luma (y, x) uses chroma (y >> 1, x >> 1), so a pixel's
 // taps share their pair along an axis whenever both fall in one chroma cell (always when s0 is even).
+//
+// VIEWS is the same body once more with the geometry read per output frame from a device table [V, 9]
+// (box_y, box_x, box_h, box_w, new_h, new_w, win_y, win_x, flags): output frame f is frame f % T of view
+// f / T, the picture cv2.resize(img[box], (new_w, new_h))[win : win + S], mirrored along x where flags & 1.
+// A block never spans two frames, so the nine ints are wave-uniform loads.  The taps are formed against the
+// box (they clamp at its edges) and then moved by the box origin, so the YUV chroma cell is the absolute
+// one.  load_view clamps the table: no table can make a tap leave the frame.
 #include "vp_common.h"
 #include "vp_kernels.h"
 
@@ -52,6 +59,59 @@ __device__ __forceinline__ uint32_t blend_rows(const Tap& ty, int h0, int h1) {
   return (uint32_t)((((ty.a0 * (h0 >> 4)) >> 16) + ((ty.a1 * (h1 >> 4)) >> 16) + 2) >> 2);
 }
 
+// What an output frame is cut from: the source box that is resized, the scales of that resize, the
+// window's origin in it and the mirror.  Without a view table the box is the frame and nothing is mirrored.
+struct Geometry {
+  int by, bx, bh, bw;       // source box
+  int y0, x0;               // window origin in the resized box
+  double scale_y, scale_x;  // 1 / (new / box), cv2's double
+  bool flip;
+};
+
+// One row of the view table, clamped: the box lies inside the H x W frame and holds a pixel, the resize is
+// S .. 2^24 - 1 a side, the window lies inside the resize.  A valid row passes through unchanged.
+__device__ __forceinline__ Geometry load_view(const int32_t* __restrict__ v, int H, int W, int S) {
+  Geometry w;
+  w.by = min(max(v[0], 0), H - 1);
+  w.bx = min(max(v[1], 0), W - 1);
+  w.bh = min(max(v[2], 1), H - w.by);
+  w.bw = min(max(v[3], 1), W - w.bx);
+  const int nh = min(max(v[4], S), (1 << 24) - 1);
+  const int nw = min(max(v[5], S), (1 << 24) - 1);
+  w.y0 = min(max(v[6], 0), nh - S);
+  w.x0 = min(max(v[7], 0), nw - S);
+  w.flip = (v[8] & 1) != 0;
+  w.scale_y = 1.0 / ((double)nh / (double)w.bh);  // the host's expression: correctly rounded divisions
+  w.scale_x = 1.0 / ((double)nw / (double)w.bw);
+  return w;
+}
+
+// Geometry of output frame f: row f / T of the table (wave-uniform: a block lies in one frame), or the
+// launch's own.
+template <bool VIEWS, typename Args>
+__device__ __forceinline__ Geometry frame_geometry(const Args& a, int f) {
+  if constexpr (VIEWS) {
+    return load_view(a.views + (int64_t)(f / a.T) * 9, a.H, a.W, a.S);
+  } else {
+    return Geometry{0, 0, a.H, a.W, a.y0, a.x0, a.scale_y, a.scale_x, false};
+  }
+}
+
+// The taps of output row oy / column ox in frame coordinates: formed against the box, so they clamp at its
+// edges, then moved by its origin.  A mirrored frame's column ox shows the window's column S - 1 - ox.
+__device__ __forceinline__ Tap row_tap(const Geometry& g, int oy) {
+  Tap t = axis_tap(g.y0 + oy, g.scale_y, g.bh);
+  t.s0 += g.by;
+  t.s1 += g.by;
+  return t;
+}
+__device__ __forceinline__ Tap col_tap(const Geometry& g, int ox, int S) {
+  Tap t = axis_tap(g.x0 + (g.flip ? S - 1 - ox : ox), g.scale_x, g.bw);
+  t.s0 += g.bx;
+  t.s1 += g.bx;
+  return t;
+}
+
 // The 4 pixels p0 .. p0+3 of a frame's flat pixel array `out` (SS pixels): three dword stores when the
 // frame's base is 4-byte aligned and the group is whole, byte stores otherwise.
 __device__ __forceinline__ void store_group(uint8_t* __restrict__ out, int p0, int SS, const uint32_t (&px)[4][3]) {
@@ -85,11 +145,20 @@ struct PreArgs {
   int blocks_per_frame;
 };
 
-__global__ __launch_bounds__(256) void preprocess_frames_kernel(const PreArgs a) {
+// The view variants' arguments behind the plain ones', whose layout stays as it is.
+struct ViewTable {
+  const int32_t* views;  // [V, 9]
+  int T;                 // output frames per view
+};
+struct PreViewArgs : PreArgs, ViewTable {};
+
+template <bool VIEWS>
+__global__ __launch_bounds__(256) void preprocess_frames_kernel(const std::conditional_t<VIEWS, PreViewArgs, PreArgs> a) {
   const int f = blockIdx.x / a.blocks_per_frame;
   const int g = (blockIdx.x - f * a.blocks_per_frame) * 256 + threadIdx.x;
   if (g >= a.groups) return;
   int n = f;
+  if constexpr (VIEWS) n = f % a.T;
   if (a.frame_idx) n = min(max(a.frame_idx[f], 0), a.N - 1);
   const uint8_t* __restrict__ frame = a.src + (int64_t)n * a.frame_stride;
   const int SS = a.S * a.S;
@@ -97,13 +166,14 @@ __global__ __launch_bounds__(256) void preprocess_frames_kernel(const PreArgs a)
   const int p0 = 4 * g;
   int oy = p0 / a.S, ox = p0 - oy * a.S;
   const int c0 = a.swap_rb ? 2 : 0, c2 = 2 - c0;
+  const Geometry geo = frame_geometry<VIEWS>(a, f);
 
   uint32_t px[4][3];
-  Tap ty = axis_tap(a.y0 + oy, a.scale_y, a.H);
+  Tap ty = row_tap(geo, oy);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (p0 + j < SS) {
-      const Tap tx = axis_tap(a.x0 + ox, a.scale_x, a.W);
+      const Tap tx = col_tap(geo, ox, a.S);
       const uint8_t* r0 = frame + (int64_t)ty.s0 * a.row_stride;
       const uint8_t* r1 = frame + (int64_t)ty.s1 * a.row_stride;
       const int o0 = 3 * tx.s0, o1 = 3 * tx.s1;
@@ -120,7 +190,7 @@ __global__ __launch_bounds__(256) void preprocess_frames_kernel(const PreArgs a)
     if (j < 3 && ++ox == a.S) {  // the group runs over a row's end (S % 4 != 0 only)
       ox = 0;
       ++oy;
-      if (p0 + j + 1 < SS) ty = axis_tap(a.y0 + oy, a.scale_y, a.H);
+      if (p0 + j + 1 < SS) ty = row_tap(geo, oy);
     }
   }
   store_group(out, p0, SS, px);
@@ -140,6 +210,7 @@ struct YuvArgs {
   int x0, y0;
   int groups, blocks_per_frame;
 };
+struct YuvViewArgs : YuvArgs, ViewTable {};
 
 // What one chroma sample adds to R, G, B before the shift: cu*(U - coff) + cv*(V - coff) + 32768.
 struct Chroma {
@@ -204,12 +275,13 @@ __device__ __forceinline__ int yuv_channel(const YuvArgs& a, int k, int luma, co
   return min(max((a.coef[k][0] * luma + c.t[k]) >> 16, 0), 255);
 }
 
-template <int FMT, bool PAIR>
-__global__ __launch_bounds__(256) void preprocess_yuv_kernel(const YuvArgs a) {
+template <int FMT, bool PAIR, bool VIEWS>
+__global__ __launch_bounds__(256) void preprocess_yuv_kernel(const std::conditional_t<VIEWS, YuvViewArgs, YuvArgs> a) {
   const int f = blockIdx.x / a.blocks_per_frame;
   const int g = (blockIdx.x - f * a.blocks_per_frame) * 256 + threadIdx.x;
   if (g >= a.groups) return;
   int n = f;
+  if constexpr (VIEWS) n = f % a.T;
   if (a.frame_idx) n = min(max(a.frame_idx[f], 0), a.N - 1);
   const uint8_t* __restrict__ py = a.plane[0] + (int64_t)n * a.frame_stride[0];
   const uint8_t* __restrict__ pu = a.plane[1] + (int64_t)n * a.frame_stride[1];
@@ -218,13 +290,14 @@ __global__ __launch_bounds__(256) void preprocess_yuv_kernel(const YuvArgs a) {
   uint8_t* __restrict__ out = a.dst + (int64_t)f * SS * 3;
   const int p0 = 4 * g;
   int oy = p0 / a.S, ox = p0 - oy * a.S;
+  const Geometry geo = frame_geometry<VIEWS>(a, f);
 
   uint32_t px[4][3];
-  Tap ty = axis_tap(a.y0 + oy, a.scale_y, a.H);
+  Tap ty = row_tap(geo, oy);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (p0 + j < SS) {
-      const Tap tx = axis_tap(a.x0 + ox, a.scale_x, a.W);
+      const Tap tx = col_tap(geo, ox, a.S);
       const uint8_t* r0 = py + (int64_t)ty.s0 * a.row_stride[0];
       const uint8_t* r1 = py + (int64_t)ty.s1 * a.row_stride[0];
       const int l00 = load_luma<FMT>(a, r0, tx.s0), l01 = load_luma<FMT>(a, r0, tx.s1);
@@ -252,17 +325,58 @@ __global__ __launch_bounds__(256) void preprocess_yuv_kernel(const YuvArgs a) {
     if (j < 3 && ++ox == a.S) {  // the group runs over a row's end (S % 4 != 0 only)
       ox = 0;
       ++oy;
-      if (p0 + j + 1 < SS) ty = axis_tap(a.y0 + oy, a.scale_y, a.H);
+      if (p0 + j + 1 < SS) ty = row_tap(geo, oy);
     }
   }
   store_group(out, p0, SS, px);
 }
 
-template <int FMT, bool PAIR>
-hipError_t launch_yuv(const YuvArgs& a, int64_t blocks, hipStream_t s) {
-  VP_NOTE_KERNEL((preprocess_yuv_kernel<FMT, PAIR>));
-  hipLaunchKernelGGL((preprocess_yuv_kernel<FMT, PAIR>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+template <int FMT, bool PAIR, typename Args>
+hipError_t launch_yuv(const Args& a, int64_t blocks, hipStream_t s) {
+  constexpr bool VIEWS = std::is_same<Args, YuvViewArgs>::value;
+  VP_NOTE_KERNEL((preprocess_yuv_kernel<FMT, PAIR, VIEWS>));
+  hipLaunchKernelGGL((preprocess_yuv_kernel<FMT, PAIR, VIEWS>), dim3((unsigned)blocks), dim3(256), 0, s, a);
   return hipGetLastError();
+}
+
+// The kernel for the planes' format and alignment (PAIR where every interleaved pair is one aligned load)
+template <typename Args>
+hipError_t launch_yuv_format(const YuvPlanes& src, const Args& a, int64_t blocks, hipStream_t s) {
+  // the low bits every interleaved pair's address shares: a pair is one load only where these make it aligned
+  const uintptr_t chroma_bits = (uintptr_t)src.plane[1] | (uintptr_t)src.row_stride[1] | (uintptr_t)src.frame_stride[1];
+  switch (src.format) {
+    case YUV_NV12:
+      return (chroma_bits & 1) == 0 ? launch_yuv<YUV_NV12, true>(a, blocks, s) : launch_yuv<YUV_NV12, false>(a, blocks, s);
+    case YUV_I420:
+      return launch_yuv<YUV_I420, false>(a, blocks, s);
+    case YUV_P010:
+      if (((uintptr_t)src.plane[0] | (uintptr_t)src.row_stride[0] | (uintptr_t)src.frame_stride[0] | chroma_bits) & 1)
+        return hipErrorInvalidValue;
+      return (chroma_bits & 3) == 0 ? launch_yuv<YUV_P010, true>(a, blocks, s) : launch_yuv<YUV_P010, false>(a, blocks, s);
+  }
+  return hipErrorInvalidValue;
+}
+
+// groups and blocks per frame of S x S output; false if F frames are more than one launch takes
+bool launch_shape(int64_t N, int64_t H, int64_t W, int64_t S, int64_t F, int64_t* groups, int64_t* bpf) {
+  *groups = (S * S + 3) / 4;
+  *bpf = (*groups + 255) / 256;
+  return !(N > INT32_MAX || H >= (1 << 24) || W >= (1 << 24) || S > 16384 || *bpf * F > INT32_MAX);
+}
+
+void fill_yuv_args(YuvArgs& a, const YuvPlanes& src, const int32_t coef[11], const int32_t* frame_idx, uint8_t* dst,
+                   int64_t N, int64_t H, int64_t W, int64_t S, int64_t groups, int64_t bpf) {
+  for (int p = 0; p < 3; ++p) {
+    a.plane[p] = static_cast<const uint8_t*>(src.plane[p]);
+    a.row_stride[p] = src.row_stride[p];
+    a.frame_stride[p] = src.frame_stride[p];
+  }
+  a.frame_idx = frame_idx; a.dst = dst;
+  for (int i = 0; i < 9; ++i) a.coef[i / 3][i % 3] = coef[i];
+  a.yoff = coef[9]; a.coff = coef[10];
+  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.S = (int)S;
+  a.groups = (int)groups;
+  a.blocks_per_frame = (int)bpf;
 }
 
 }  // namespace
@@ -288,11 +402,9 @@ const char* preprocess_geometry(int64_t H, int64_t W, int64_t S, int mode, int64
 hipError_t preprocess_frames(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
                              int64_t frame_stride, const int32_t* frame_idx, int64_t F, int mode, int swap_rb,
                              int64_t S, uint8_t* dst, hipStream_t s) {
-  int64_t new_h, new_w, y0, x0;
+  int64_t new_h, new_w, y0, x0, groups, bpf;
   if (preprocess_geometry(H, W, S, mode, &new_h, &new_w, &y0, &x0)) return hipErrorInvalidValue;
-  const int64_t groups = (S * S + 3) / 4;
-  const int64_t bpf = (groups + 255) / 256;
-  if (N > INT32_MAX || H >= (1 << 24) || W >= (1 << 24) || S > 16384 || bpf * F > INT32_MAX) return hipErrorInvalidValue;
+  if (!launch_shape(N, H, W, S, F, &groups, &bpf)) return hipErrorInvalidValue;
   PreArgs a;
   a.src = src; a.frame_idx = frame_idx; a.dst = dst;
   a.row_stride = row_stride; a.frame_stride = frame_stride;
@@ -304,8 +416,28 @@ hipError_t preprocess_frames(const uint8_t* src, int64_t N, int64_t H, int64_t W
   a.swap_rb = swap_rb ? 1 : 0;
   a.groups = (int)groups;
   a.blocks_per_frame = (int)bpf;
-  VP_NOTE_KERNEL(preprocess_frames_kernel);
-  hipLaunchKernelGGL(preprocess_frames_kernel, dim3((unsigned)(bpf * F)), dim3(256), 0, s, a);
+  VP_NOTE_KERNEL(preprocess_frames_kernel<false>);
+  hipLaunchKernelGGL(preprocess_frames_kernel<false>, dim3((unsigned)(bpf * F)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t preprocess_views(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
+                            int64_t frame_stride, const int32_t* frame_idx, const int32_t* views, int64_t V,
+                            int64_t T, int swap_rb, int64_t S, uint8_t* dst, hipStream_t s) {
+  int64_t groups, bpf;
+  if (V * T > INT32_MAX || !launch_shape(N, H, W, S, V * T, &groups, &bpf)) return hipErrorInvalidValue;
+  PreViewArgs a;
+  a.src = src; a.frame_idx = frame_idx; a.dst = dst;
+  a.row_stride = row_stride; a.frame_stride = frame_stride;
+  a.scale_x = a.scale_y = 0.0;  // the table's
+  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.S = (int)S;
+  a.x0 = a.y0 = 0;
+  a.swap_rb = swap_rb ? 1 : 0;
+  a.groups = (int)groups;
+  a.blocks_per_frame = (int)bpf;
+  a.views = views; a.T = (int)T;
+  VP_NOTE_KERNEL(preprocess_frames_kernel<true>);
+  hipLaunchKernelGGL(preprocess_frames_kernel<true>, dim3((unsigned)(bpf * V * T)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -328,40 +460,28 @@ const char* yuv_coefficients(int matrix, int range, int bit_depth, int32_t out[1
 
 hipError_t preprocess_yuv(const YuvPlanes& src, const int32_t coef[11], int64_t N, int64_t H, int64_t W,
                           const int32_t* frame_idx, int64_t F, int mode, int64_t S, uint8_t* dst, hipStream_t s) {
-  int64_t new_h, new_w, y0, x0;
+  int64_t new_h, new_w, y0, x0, groups, bpf;
   if (preprocess_geometry(H, W, S, mode, &new_h, &new_w, &y0, &x0)) return hipErrorInvalidValue;
-  const int64_t groups = (S * S + 3) / 4;
-  const int64_t bpf = (groups + 255) / 256;
-  if (N > INT32_MAX || H >= (1 << 24) || W >= (1 << 24) || S > 16384 || bpf * F > INT32_MAX) return hipErrorInvalidValue;
+  if (!launch_shape(N, H, W, S, F, &groups, &bpf)) return hipErrorInvalidValue;
   YuvArgs a;
-  for (int p = 0; p < 3; ++p) {
-    a.plane[p] = static_cast<const uint8_t*>(src.plane[p]);
-    a.row_stride[p] = src.row_stride[p];
-    a.frame_stride[p] = src.frame_stride[p];
-  }
-  // the low bits every interleaved pair's address shares: a pair is one load only where these make it aligned
-  const uintptr_t chroma_bits = (uintptr_t)src.plane[1] | (uintptr_t)src.row_stride[1] | (uintptr_t)src.frame_stride[1];
-  a.frame_idx = frame_idx; a.dst = dst;
+  fill_yuv_args(a, src, coef, frame_idx, dst, N, H, W, S, groups, bpf);
   a.scale_x = 1.0 / ((double)new_w / (double)W);
   a.scale_y = 1.0 / ((double)new_h / (double)H);
-  for (int i = 0; i < 9; ++i) a.coef[i / 3][i % 3] = coef[i];
-  a.yoff = coef[9]; a.coff = coef[10];
-  a.N = (int)N; a.H = (int)H; a.W = (int)W; a.S = (int)S;
   a.x0 = (int)x0; a.y0 = (int)y0;
-  a.groups = (int)groups;
-  a.blocks_per_frame = (int)bpf;
-  const int64_t blocks = bpf * F;
-  switch (src.format) {
-    case YUV_NV12:
-      return (chroma_bits & 1) == 0 ? launch_yuv<YUV_NV12, true>(a, blocks, s) : launch_yuv<YUV_NV12, false>(a, blocks, s);
-    case YUV_I420:
-      return launch_yuv<YUV_I420, false>(a, blocks, s);
-    case YUV_P010:
-      if (((uintptr_t)src.plane[0] | (uintptr_t)src.row_stride[0] | (uintptr_t)src.frame_stride[0] | chroma_bits) & 1)
-        return hipErrorInvalidValue;
-      return (chroma_bits & 3) == 0 ? launch_yuv<YUV_P010, true>(a, blocks, s) : launch_yuv<YUV_P010, false>(a, blocks, s);
-  }
-  return hipErrorInvalidValue;
+  return launch_yuv_format(src, a, bpf * F, s);
+}
+
+hipError_t preprocess_yuv_views(const YuvPlanes& src, const int32_t coef[11], int64_t N, int64_t H, int64_t W,
+                                const int32_t* frame_idx, const int32_t* views, int64_t V, int64_t T, int64_t S,
+                                uint8_t* dst, hipStream_t s) {
+  int64_t groups, bpf;
+  if (V * T > INT32_MAX || !launch_shape(N, H, W, S, V * T, &groups, &bpf)) return hipErrorInvalidValue;
+  YuvViewArgs a;
+  fill_yuv_args(a, src, coef, frame_idx, dst, N, H, W, S, groups, bpf);
+  a.scale_x = a.scale_y = 0.0;  // the table's
+  a.x0 = a.y0 = 0;
+  a.views = views; a.T = (int)T;
+  return launch_yuv_format(src, a, bpf * V * T, s);
 }
 
 }  // namespace vp

@@ -914,26 +914,28 @@ int vp_dev_yuv_coefficients(int matrix, int range, int bit_depth, int32_t out[11
   return VP_OK;
 }
 
-int vp_op_preprocess_yuv(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t W, const int32_t* frame_idx,
-                         int64_t F, int mode, int64_t S, uint8_t* dst, void* stream) {
+namespace {
+// The checks vp_op_preprocess_yuv and vp_op_preprocess_yuv_views share, in the former's order: the planes of a
+// vp_yuv_frames for N frames of H x W, F output frames of S x S (mode: the resize mode where the call has one)
+// -> the kernel's planes and coefficient table, or the error
+int yuv_source(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t W, int64_t F, int64_t S, const int* mode,
+               const uint8_t* dst, vp::YuvPlanes& pl, int32_t coef[11]) {
   using namespace vp;
   if (!src || !src->plane[0] || !dst) return fail(VP_EINVAL, "null argument");
   const int fmt = src->format;
   if (fmt != VP_YUV_NV12 && fmt != VP_YUV_I420 && fmt != VP_YUV_P010)
     return fail(VP_EINVAL, "Unknown pixel format: " + std::to_string(fmt));
-  int32_t coef[11];
   if (const char* why = yuv_coefficients(src->matrix, src->range, fmt == VP_YUV_P010 ? 10 : 8, coef))
     return fail(VP_EINVAL, why);
   const int planes = fmt == VP_YUV_I420 ? 3 : 2;
   for (int p = 1; p < planes; ++p)
     if (!src->plane[p]) return fail(VP_EINVAL, "missing chroma plane");
   if (N < 1 || H < 1 || W < 1 || F < 1 || S < 1) return fail(VP_EINVAL, "N, H, W, F and S must be at least 1");
-  if (mode != VP_RESIZE_CENTER_CROP && mode != VP_RESIZE_STRETCH)
-    return fail(VP_EINVAL, "Unknown resize_mode: " + std::to_string(mode));
+  if (mode && *mode != VP_RESIZE_CENTER_CROP && *mode != VP_RESIZE_STRETCH)
+    return fail(VP_EINVAL, "Unknown resize_mode: " + std::to_string(*mode));
   if (H >= (1 << 24) || W >= (1 << 24) || S > 16384 || N > INT32_MAX || F > INT32_MAX)
     return fail(VP_EINVAL, "frame geometry out of range (H, W < 2^24, S <= 16384, N, F < 2^31)");
   const int64_t sample = fmt == VP_YUV_P010 ? 2 : 1, ch = (H + 1) / 2, cw = (W + 1) / 2;
-  YuvPlanes pl;
   pl.format = fmt;
   for (int p = 0; p < 3; ++p) {
     pl.plane[p] = p < planes ? src->plane[p] : nullptr;
@@ -948,6 +950,65 @@ int vp_op_preprocess_yuv(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t
     if (fmt == VP_YUV_P010 && (((uintptr_t)pl.plane[p] | (uintptr_t)pl.row_stride[p] | (uintptr_t)pl.frame_stride[p]) & 1))
       return fail(VP_EINVAL, "P010 plane bases and strides must be multiples of 2 bytes");
   }
+  return VP_OK;
+}
+
+// V views of T frames each: the arguments the two view calls add
+int check_views(const int32_t* views, int64_t V, int64_t T) {
+  if (!views) return fail(VP_EINVAL, "null argument");
+  if (V < 1 || T < 1) return fail(VP_EINVAL, "V and T must be at least 1");
+  if (V > INT32_MAX || T > INT32_MAX || V * T > INT32_MAX)
+    return fail(VP_EINVAL, "frame geometry out of range (V * T < 2^31)");
+  return VP_OK;
+}
+
+// without frame_idx, frame t of every view is source frame t
+int check_view_frames(const int32_t* frame_idx, int64_t N, int64_t T) {
+  if (!frame_idx && T > N)
+    return fail(VP_EINVAL, "Video has only " + std::to_string(N) + " frames, but " + std::to_string(T) + " requested");
+  return VP_OK;
+}
+}  // namespace
+
+int vp_op_preprocess_views(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
+                           int64_t frame_stride, const int32_t* frame_idx, const int32_t* views, int64_t V,
+                           int64_t T, int swap_rb, int64_t S, uint8_t* dst, void* stream) {
+  using namespace vp;
+  if (!src || !dst) return fail(VP_EINVAL, "null argument");
+  if (int rc = check_views(views, V, T)) return rc;
+  if (N < 1 || H < 1 || W < 1 || S < 1) return fail(VP_EINVAL, "N, H, W and S must be at least 1");
+  if (H >= (1 << 24) || W >= (1 << 24) || S > 16384 || N > INT32_MAX)
+    return fail(VP_EINVAL, "frame geometry out of range (H, W < 2^24, S <= 16384, N < 2^31)");
+  if (row_stride < 3 * W) return fail(VP_EINVAL, "row_stride must be at least 3*W bytes");
+  if (frame_stride < H * row_stride) return fail(VP_EINVAL, "frame_stride must be at least H*row_stride bytes");
+  if (int rc = check_view_frames(frame_idx, N, T)) return rc;
+  hipError_t e = preprocess_views(src, N, H, W, row_stride, frame_stride, frame_idx, views, V, T, swap_rb, S, dst,
+                                  static_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) return fail(VP_EINVAL, "too many output pixels for one launch");
+  VP_HIP(e);
+  return VP_OK;
+}
+
+int vp_op_preprocess_yuv_views(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t W, const int32_t* frame_idx,
+                               const int32_t* views, int64_t V, int64_t T, int64_t S, uint8_t* dst, void* stream) {
+  using namespace vp;
+  if (int rc = check_views(views, V, T)) return rc;
+  YuvPlanes pl;
+  int32_t coef[11];
+  if (int rc = yuv_source(src, N, H, W, V * T, S, nullptr, dst, pl, coef)) return rc;
+  if (int rc = check_view_frames(frame_idx, N, T)) return rc;
+  hipError_t e = preprocess_yuv_views(pl, coef, N, H, W, frame_idx, views, V, T, S, dst, static_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) return fail(VP_EINVAL, "too many output pixels for one launch");
+  VP_HIP(e);
+  return VP_OK;
+}
+
+int vp_op_preprocess_yuv(const vp_yuv_frames* src, int64_t N, int64_t H, int64_t W, const int32_t* frame_idx,
+                         int64_t F, int mode, int64_t S, uint8_t* dst, void* stream) {
+  using namespace vp;
+  YuvPlanes pl;
+  int32_t coef[11];
+  if (int rc = yuv_source(src, N, H, W, F, S, &mode, dst, pl, coef)) return rc;
   if (!frame_idx && F > N)
     return fail(VP_EINVAL, "Video has only " + std::to_string(N) + " frames, but " + std::to_string(F) + " requested");
   int64_t nh, nw, y0, x0;

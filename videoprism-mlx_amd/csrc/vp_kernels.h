@@ -350,5 +350,15 @@ const char* yuv_coefficients(int matrix, int range, int bit_depth, int32_t out[1
 // coef: yuv_coefficients' table.  P010 planes and strides must be 2-byte aligned (hipErrorInvalidValue)
 hipError_t preprocess_yuv(const YuvPlanes& src, const int32_t coef[11], int64_t N, int64_t H, int64_t W,
                           const int32_t* frame_idx, int64_t F, int mode, int64_t S, uint8_t* dst, hipStream_t s);
+// Both once more with the geometry per output frame: views is a device table int32 [V, 9] of (box_y, box_x,
+// box_h, box_w, new_h, new_w, win_y, win_x, flags) rows, which the kernel clamps; output frame v*T + t is
+// cv2.resize(frame[box], (new_w, new_h))[win : win + S], mirrored along x where flags & 1, of source frame
+// frame_idx[v*T + t] (nullable: t) -> dst uint8 [V*T, S, S, 3]
+hipError_t preprocess_views(const uint8_t* src, int64_t N, int64_t H, int64_t W, int64_t row_stride,
+                            int64_t frame_stride, const int32_t* frame_idx, const int32_t* views, int64_t V,
+                            int64_t T, int swap_rb, int64_t S, uint8_t* dst, hipStream_t s);
+hipError_t preprocess_yuv_views(const YuvPlanes& src, const int32_t coef[11], int64_t N, int64_t H, int64_t W,
+                                const int32_t* frame_idx, const int32_t* views, int64_t V, int64_t T, int64_t S,
+                                uint8_t* dst, hipStream_t s);
 
 }  // namespace vp

@@ -168,6 +168,11 @@ _SIGNATURES = {
                                         c_int64, c_int, c_int, c_int64, c_void_p, c_void_p]),
     "vp_op_preprocess_yuv": (c_int, [POINTER(vp_yuv_frames), c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
                                      c_int64, c_void_p, c_void_p]),
+    # the same two with a device table of views [V, 9] in place of the resize mode
+    "vp_op_preprocess_views": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                       c_int64, c_int64, c_int, c_int64, c_void_p, c_void_p]),
+    "vp_op_preprocess_yuv_views": (c_int, [POINTER(vp_yuv_frames), c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                           c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     # the conversion's integer table (tests/yuv_restatement.py); no GPU call
     "vp_dev_yuv_coefficients": (c_int, [c_int, c_int, c_int, POINTER(c_int32)]),
     "vp_op_pool_l2": (c_int, [c_void_p, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
@@ -1119,6 +1124,45 @@ def op_preprocess_frames(src, frame_idx=None, mode=VP_RESIZE_CENTER_CROP, swap_r
     return out
 
 
+def _views_args(views, frame_idx, N, size, out, device):
+    """(V, T, out) of a view launch: views int32 [V, 9] and frame_idx int32 [V, T] (None: T = N, frame t of every
+    view is source frame t), both contiguous on `device`; out uint8 [V * T, size, size, 3]."""
+    import torch
+    if (views.dtype != torch.int32 or views.dim() != 2 or views.shape[1] != 9 or views.shape[0] < 1 or
+            not views.is_contiguous() or views.device != device):
+        raise ValueError("views must be a contiguous int32 [V, 9] table on the frames' device")
+    V = views.shape[0]
+    if frame_idx is not None and (frame_idx.dtype != torch.int32 or frame_idx.dim() != 2 or frame_idx.shape[0] != V or
+                                  not frame_idx.is_contiguous() or frame_idx.device != device):
+        raise ValueError(f"frame_idx must be a contiguous int32 [{V}, T] matrix on the frames' device")
+    T = N if frame_idx is None else frame_idx.shape[1]
+    if out is None:
+        out = torch.empty((V * T, size, size, 3), dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (V * T, size, size, 3) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous uint8 {(V * T, size, size, 3)}")
+    return V, T, out
+
+
+def op_preprocess_views(src, views, frame_idx=None, swap_rb=False, size=288, out=None, stream=None):
+    """op_preprocess_frames with the geometry per output frame: views int32 [V, 9] on the device (rows box_y, box_x,
+    box_h, box_w, new_h, new_w, win_y, win_x, flags; clamped by the kernel, see vp_op_preprocess_views), frame_idx
+    int32 [V, T] on the device (None: all N frames for every view) -> uint8 [V * T, size, size, 3], view-major."""
+    import torch
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise ValueError(f"frames must be uint8 [N, H, W, 3], got {src.dtype} {tuple(src.shape)}")
+    N, H, W, _ = src.shape
+    if src.stride(3) != 1 or (W > 1 and src.stride(2) != 3):
+        raise ValueError("frames must have packed pixels (channel stride 1, pixel stride 3)")
+    # a dimension of extent 1 may carry any stride: give the packed one
+    row_stride = src.stride(1) if H > 1 else 3 * W
+    frame_stride = src.stride(0) if N > 1 else H * row_stride
+    V, T, out = _views_args(views, frame_idx, N, size, out, src.device)
+    with torch.cuda.device(src.device):  # the entry point has no handle: it launches on the current device
+        call("vp_op_preprocess_views", _ptr(src), N, H, W, row_stride, frame_stride, _ptr(frame_idx), _ptr(views), V, T,
+             1 if swap_rb else 0, size, _ptr(out), _stream(stream))
+    return out
+
+
 def op_pool_l2(emb, stream=None):
     import torch
     B, L, D = emb.shape
@@ -1236,4 +1280,18 @@ def op_preprocess_yuv(planes, pixel_format=VP_YUV_NV12, matrix=VP_YUV_BT601, col
     with torch.cuda.device(y.device):  # the entry point has no handle: it launches on the current device
         call("vp_op_preprocess_yuv", ctypes.byref(src), N, H, W, _ptr(frame_idx), F, int(mode), size, _ptr(out),
              _stream(stream))
+    return out
+
+
+def op_preprocess_yuv_views(planes, views, pixel_format=VP_YUV_NV12, matrix=VP_YUV_BT601, color_range=VP_YUV_LIMITED,
+                            frame_idx=None, size=288, out=None, stream=None):
+    """op_preprocess_views on the RGB frames that 4:2:0 decoder planes stand for (see yuv_frames; read in place, the
+    RGB frames are never stored): views int32 [V, 9], frame_idx int32 [V, T] or None -> uint8 [V * T, size, size, 3]."""
+    import torch
+    src, N, H, W = yuv_frames(planes, pixel_format, matrix, color_range)
+    y = planes[0]
+    V, T, out = _views_args(views, frame_idx, N, size, out, y.device)
+    with torch.cuda.device(y.device):  # the entry point has no handle: it launches on the current device
+        call("vp_op_preprocess_yuv_views", ctypes.byref(src), N, H, W, _ptr(frame_idx), _ptr(views), V, T, size,
+             _ptr(out), _stream(stream))
     return out
